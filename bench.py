@@ -11,9 +11,15 @@ Workload = BASELINE.json configs[1]: full R-Super 3D UNet (base 32, 26 PanTS cla
 96^3 patches, batch 2 per GPU, segmentation loss (masked BCE + adaptive-Tversky Dice), report losses off.
 Rank 0 prints ONE JSON line; `value` = voxels processed by all ranks / max-over-ranks time of the K timed steps.
 
-The timed region contains nothing but the K steps (no event records).  The roofline numbers come from a separate pass
-AFTER it (same model, same batch, HIP events around every conv MFMA launch on the launch stream); at N = 1 further short
-legs report config 3 (report supervision), the f32 parity mode and the cost of bf16 (`secondary`), then the CPU baseline.
+The timed region contains nothing but the K steps (no event records).  A plain run stops there: set-up, W warm-up steps,
+the K timed steps, the outputs (--dump-outputs DIR), the JSON line.  With --full the roofline numbers come from a separate
+pass AFTER it (same model, same batch, HIP events around every conv MFMA launch on the launch stream); at N = 1 further
+short legs report config 3 (report supervision), the f32 parity mode and the cost of bf16 (`secondary`), then the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step handed its caller and left in the model, as .npy files (rank 0): every
+loss term and the pre-clip gradient norm (float64), and a fixed seeded sample of the updated parameters, their EMA and
+their gradients (float32, DUMP_SAMPLE elements each, in parameter order).  Weights and batch are seeded: the same
+arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -35,6 +41,7 @@ MFMA_PEAK_TFLOPS = {'bf16': 2500.0, 'f32': 157.3}     # dense, /opt/skills/guide
 # Fabric-side bytes (FETCH_SIZE x2 + WRITE_SIZE) of the conv MFMA launches of ONE default step are read from this file
 # (written by tools/pmc_step_summary.py from the rocprofv3 --pmc passes of tools/pmc_step.sh; see its "source" key).
 TRAFFIC_PROFILE = os.path.join(ROOT, 'profiles', 'conv_traffic.json')
+DUMP_SAMPLE = 1 << 22          # elements per sampled array of --dump-outputs: 3 x 16 MiB of float32 (40.56 M parameters at base 32)
 
 
 def conv_stack_flops(base, S, B):
@@ -106,6 +113,31 @@ def cpu_baseline(args, classes):
             'sample': f'{nsteps} timed full training steps (fwd + seg loss + bwd + clip + AdamW + EMA) of the fp32 torch-CPU oracle after 1 warm-up step of the '
                       f'same shape, B={B}, {S}^3, base {base}, {len(classes)} classes, {ncores} threads: mean {dt:.1f} s/step '
                       f'(min {min(ts):.1f}, max {max(ts):.1f}, warm-up {t_warm:.1f})'}
+
+
+def dump_outputs(leg, out_dir):
+    """The results of the leg's last step as DIR/<name>.npy (see the module docstring)."""
+    os.makedirs(out_dir, exist_ok=True)
+    losses, gnorm = leg.last
+    arrays = {f'loss_{k}': np.asarray(torch.as_tensor(v).detach().double().cpu()) for k, v in losses.items() if v is not None}
+    if gnorm is not None:
+        arrays['grad_norm'] = np.asarray(torch.as_tensor(gnorm).detach().double().cpu())
+    params = list(leg.net.parameters())
+    n = sum(p.numel() for p in params)
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, size=DUMP_SAMPLE, replace=False))
+    idx = torch.from_numpy(idx).to(params[0].device)
+
+    def sample(ts):
+        return torch.cat([t.detach().float().reshape(-1) for t in ts]).index_select(0, idx).cpu().numpy()
+    with torch.no_grad():
+        arrays['params_sample'] = sample(params)
+        arrays['ema_params_sample'] = sample(list(leg.ema.parameters()))
+        grads = [p.grad for p in params]
+        if any(g is None for g in grads):
+            raise RuntimeError('--dump-outputs: a parameter has no gradient after the last timed step')
+        arrays['grads_sample'] = sample(grads)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def respawn_under_torchrun(args):
@@ -428,10 +460,14 @@ def main():
     ap.add_argument('--guards', type=int, default=1, help="1: the reference's per-step guards run inside the timed region as device-side flags (default); 0: off")
     ap.add_argument('--no-secondary', action='store_true', help='skip the config-3 / f32 / bf16-vs-f32 legs')
     ap.add_argument('--unpacked-labels', action='store_true', help='A/B: label / unknown / segment volumes as uint8 planes instead of the bit-packed storage form')
-    ap.add_argument('--roofline-steps', type=int, default=10, help='steps of the separate HIP-event pass after the timed region')
+    ap.add_argument('--roofline-steps', type=int, default=10, help='(--full) steps of the separate HIP-event pass after the timed region')
+    ap.add_argument('--full', action='store_true', help='after the headline: roofline pass, secondary legs (N = 1) and CPU baseline (N = 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's losses and a seeded sample of parameters / EMA / gradients as DIR/<name>.npy")
     ap.add_argument('--secondary-only', action='store_true', help='(internal) run only the secondary legs and print their JSON')
     ap.add_argument('--force-ddp', action='store_true', help='wrap in the data-parallel reducer even with one rank (exercises the RCCL path)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(respawn_under_torchrun(args))
@@ -474,13 +510,30 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     loss_val = leg.loss()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(leg, args.dump_outputs)
 
     out = None
     if rank == 0:
+        out = {
+            'metric': 'CT voxels/sec/node (96³ patch, bs=2/GPU)', 'value': world * B * S ** 3 * args.steps / dt, 'unit': 'voxels/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
+            'config': {'workload': f'R-Super 3D UNet(base {args.base}, {len(classes)} classes, BasicBlock/IN) full training step '
+                                   f'(fwd + {"seg+Volume+Ball" if args.report else "masked BCE + Dice"} loss + bwd + clip + AdamW + EMA), '
+                                   f'{S}^3 patches, batch {B}/GPU (BASELINE.json configs[{2 if args.report else 1}])' + (' -- VARIANT pool=False (strided down blocks)' if args.no_pool else ''),
+                       'global_batch': world * B, 'patch': S, 'parallelism': f'dp{world}', 'final_loss': loss_val,
+                       'label_volumes': 'uint8 planes' if args.unpacked_labels else 'bit-packed (np.packbits over classes, the dataset storage form), read packed by the loss kernels',
+                       'sanity_checks_in_timed_region': bool(args.guards),
+                       'sanity_checks_form': 'device-side flags read one step late (train_ddp.StepGuard)' if args.guards else 'off'},
+        }
+
+    # ---- --full only, below: nothing of it feeds the headline fields above
+    if args.full and rank == 0:
         # ---- roofline pass (outside the timed region): HIP events around every conv MFMA launch, on the launch stream
         timer = ops.KernelTimer()
         ops.TIMER = timer
-    if args.roofline_steps > 0:
+    if args.full and args.roofline_steps > 0:
         import gc
         gc.collect()
         gc.disable()                      # a collection between recording a start event and launching its kernel would be charged to the bracket
@@ -491,7 +544,7 @@ def main():
         leg.sync()
         gc.enable()
     ops.TIMER = None
-    if rank == 0:
+    if args.full and rank == 0:
         ksum = timer.summary()
         conv_ms_sum = sum(d['ms'] for d in ksum.values())
         # union of the launch intervals (weight gradients may overlap the data-gradient chain) over the steps within 5 % of the median step (ops.KernelTimer.summary:
@@ -508,17 +561,7 @@ def main():
         if default_wl and os.path.exists(TRAFFIC_PROFILE):
             tp = json.load(open(TRAFFIC_PROFILE))
             traffic, traffic_src = tp.get('conv_bytes_per_step'), tp.get('source')
-        out = {
-            'metric': 'CT voxels/sec/node (96³ patch, bs=2/GPU)', 'value': world * B * S ** 3 * args.steps / dt, 'unit': 'voxels/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
-            'config': {'workload': f'R-Super 3D UNet(base {args.base}, {len(classes)} classes, BasicBlock/IN) full training step '
-                                   f'(fwd + {"seg+Volume+Ball" if args.report else "masked BCE + Dice"} loss + bwd + clip + AdamW + EMA), '
-                                   f'{S}^3 patches, batch {B}/GPU (BASELINE.json configs[{2 if args.report else 1}])' + (' -- VARIANT pool=False (strided down blocks)' if args.no_pool else ''),
-                       'global_batch': world * B, 'patch': S, 'parallelism': f'dp{world}', 'final_loss': loss_val,
-                       'label_volumes': 'uint8 planes' if args.unpacked_labels else 'bit-packed (np.packbits over classes, the dataset storage form), read packed by the loss kernels',
-                       'sanity_checks_in_timed_region': bool(args.guards),
-                       'sanity_checks_form': 'device-side flags read one step late (train_ddp.StepGuard)' if args.guards else 'off'},
+        out.update({
             'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak,
                          'traffic': traffic, 'traffic_unit': 'bytes per step over all conv MFMA launches (FETCH_SIZE x2 + WRITE_SIZE)',
                          'traffic_source': traffic_src,
@@ -534,8 +577,8 @@ def main():
                          'step_level_frac': (3 * fwd_fl / (dt / args.steps)) / 1e12 / peak,
                          'per_kernel': {k: {'launches_per_step': d['launches'] / rs, 'avg_us': d['ms'] * 1e3 / d['launches'], 'max_us': d['max_ms'] * 1e3,
                                             'tflops': d['flops'] / (d['ms'] * 1e-3) / 1e12} for k, d in ksum.items()}},
-        }
-    if world == 1 and not args.no_secondary and not args.force_ddp:
+        })
+    if args.full and world == 1 and not args.no_secondary and not args.force_ddp:
         # ---- secondary legs in a child process: whatever happens there (exception, hard crash), the headline line is still printed
         leg.close()
         del leg
@@ -547,7 +590,7 @@ def main():
             out['secondary'] = json.loads(lines[-1]) if (r.returncode == 0 and lines) else {'error': f'rc {r.returncode}: ' + r.stderr.strip()[-300:]}
         except Exception as e:                           # noqa: BLE001 -- includes the timeout
             out['secondary'] = {'error': repr(e)[:300]}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         try:
             out['cpu_baseline'] = cpu_baseline(args, classes)
         except Exception as e:                           # noqa: BLE001 -- a reported baseline must not cost the headline line

@@ -489,10 +489,10 @@ def test_plane_any_matches_torch():
 
 
 @pytest.mark.gpu
-def test_bench_two_ranks_on_one_gpu_gloo():
+def test_bench_two_ranks_on_one_gpu_gloo(tmp_path):
     """The N = 2 flow of bench.py as the driver launches it (torchrun, one process per rank, GradReducer, barrier + max over
     ranks, rank-0 JSON) -- on a single-GPU box the two ranks share the device through RSUPER_DIST_BACKEND=gloo (RCCL refuses
-    duplicate devices); only RCCL's own transport is not exercised."""
+    duplicate devices); only RCCL's own transport is not exercised.  --dump-outputs: rank 0 writes the last step's results."""
     import json
     import os
     import subprocess
@@ -501,11 +501,40 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     env = dict(os.environ, RSUPER_DIST_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                         '--master-port', '29571', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--size', '64',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                        '--no-cpu-baseline', '--dump-outputs', str(tmp_path)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d['n_gpus'] == 2 and d['config']['parallelism'] == 'dp2' and d['scaling'] == 'weak'
     assert d['value'] > 0 and np.isfinite(d['config']['final_loss'])
+    dumped = {f.name[:-4]: np.load(f) for f in tmp_path.glob('*.npy')}
+    assert {'loss_overall', 'grad_norm', 'params_sample', 'ema_params_sample', 'grads_sample'} <= set(dumped)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in dumped.values())
+    assert float(dumped['loss_overall']) == d['config']['final_loss'] and sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    assert np.abs(dumped['grads_sample']).max() > 0 and not np.array_equal(dumped['params_sample'], dumped['ema_params_sample'])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """`bench.py --dump-outputs` on one GPU: the same arguments give the same inputs, so two processes dump bit-identical results of their last
+    timed step -- the losses of the result line, a non-zero gradient sample, and parameters that the step moved away from their EMA."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for name in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--size', '64',
+                            '--dump-outputs', str(tmp_path / name)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d['steps'] == 3 and 'roofline' not in d and 'secondary' not in d and 'cpu_baseline' not in d
+        runs.append((d, {f.name[:-4]: np.load(f) for f in (tmp_path / name).glob('*.npy')}))
+    (da, a), (db, b) = runs
+    assert set(a) == set(b) and {'loss_overall', 'grad_norm', 'params_sample', 'ema_params_sample', 'grads_sample'} <= set(a)
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+    assert float(a['loss_overall']) == da['config']['final_loss'] == db['config']['final_loss']
+    assert np.abs(a['grads_sample']).max() > 0 and not np.array_equal(a['params_sample'], a['ema_params_sample'])
 
 
 def test_two_ranks_match_two_reference_ranks_averaged():
@@ -536,7 +565,7 @@ def test_bench_self_spawns_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env['RSUPER_DIST_BACKEND'] = 'gloo'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--size', '64',
-                        '--roofline-steps', '1', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                        '--roofline-steps', '1', '--no-cpu-baseline', '--full'], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d['n_gpus'] == 2 and d['config']['global_batch'] == 4 and d['roofline']['frac'] > 0

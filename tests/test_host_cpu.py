@@ -13,6 +13,14 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _free_port():
+    """A port no other process holds: fixed ports collide when two checkouts run the suite at the same time."""
+    import socket
+    with socket.socket() as s:
+        s.bind(('127.0.0.1', 0))
+        return s.getsockname()[1]
+
+
 def test_library_loads_and_exports_every_declared_symbol():
     from rsuper_amd.hip import lib
     so = lib.SO_PATH
@@ -169,9 +177,10 @@ def test_shard_indices_round_robin():
 def test_ddp_world2_gloo_cpu():
     """N>1 path on CPU: two gloo ranks average gradients of a host-side module through wrap_ddp and agree."""
     script = os.path.join(ROOT, 'tests', 'ddp_gloo_worker.py')
-    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29533')
+    port = _free_port()
+    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', '29533', script], env=env, capture_output=True, text=True, timeout=300)
+                        '--master-port', str(port), script], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert 'DDP_OK' in r.stdout
 
@@ -216,9 +225,10 @@ def test_grad_reducer_world2_gloo_cpu():
     """rsuper_amd.reducer.GradReducer (the GPU default behind wrap_ddp) on two gloo ranks: rank-0 broadcast, bucketed mean
     of gradients living in the flat buckets, re-arming across steps, missing-gradient detection."""
     script = os.path.join(ROOT, 'tests', 'reducer_gloo_worker.py')
-    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29537')
+    port = _free_port()
+    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', '29537', script], env=env, capture_output=True, text=True, timeout=300)
+                        '--master-port', str(port), script], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert 'REDUCER_OK' in r.stdout
 
@@ -228,9 +238,10 @@ def test_ddp_world2_matches_two_reference_ranks_averaged():
     batches (oracle as the model on CPU), the product's GradReducer exchanges the gradients, and every parameter's exchanged gradient equals the
     mean of the UNMODIFIED reference's two ranks (tests/golden/ddp2.npz from gen_golden_ddp.py; train_ddp.py:623-668, sampler.py:132)."""
     script = os.path.join(ROOT, 'tests', 'ddp_fixture_gloo_worker.py')
-    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29545', OMP_NUM_THREADS='4')
+    port = _free_port()
+    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), OMP_NUM_THREADS='4')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', '29545', script], env=env, capture_output=True, text=True, timeout=600)
+                        '--master-port', str(port), script], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert 'DDP_FIXTURE_OK' in r.stdout
 
@@ -239,9 +250,10 @@ def test_graph_gradient_exchange_world2_gloo_cpu():
     """rsuper_amd.graph.exchange_gradients (what GraphedNetwork runs after its backward replay in a distributed run) on two gloo ranks:
     in-place mean over several flat buckets."""
     script = os.path.join(ROOT, 'tests', 'exchange_gloo_worker.py')
-    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29541')
+    port = _free_port()
+    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', '29541', script], env=env, capture_output=True, text=True, timeout=300)
+                        '--master-port', str(port), script], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert 'EXCHANGE_OK' in r.stdout
 

@@ -3,8 +3,8 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out; out=gpurun_out/nopool_ab.txt; : > $out
 for e in "" "RSUPER_S2K=0 RSUPER_S2D=0" "RSUPER_S2K=0" "RSUPER_S2D=0" "RSUPER_S2_KERNEL=0"; do
-  echo "== bench.py --no-pool --steps 20 --warmup 5 --no-secondary --no-cpu-baseline   $e" >> $out
-  env $e timeout 600 python bench.py --no-pool --steps 20 --warmup 5 --no-secondary --no-cpu-baseline 2>/dev/null | python -c "
+  echo "== bench.py --full --no-pool --steps 20 --warmup 5 --no-secondary --no-cpu-baseline   $e" >> $out
+  env $e timeout 600 python bench.py --full --no-pool --steps 20 --warmup 5 --no-secondary --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

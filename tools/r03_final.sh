@@ -6,5 +6,6 @@ RSUPER_NO_BOX=1 timeout 200 python tools/bench_conv.py bf16 2>/dev/null | grep -
 timeout 200 python tools/bench_conv.py f32 2>/dev/null | grep "s2\|stride-2" > gpurun_out/r03_conv_layers_s2_f32.txt
 timeout 300 bash tools/kstats.sh r03
 timeout 300 bash tools/mf_kstats.sh
-timeout 600 python bench.py > gpurun_out/r03_bench_default.json 2> gpurun_out/r03_bench_default.err
-tail -c 400 gpurun_out/r03_bench_default.json
+# the default bench line with everything --full adds (roofline, secondary legs, CPU baseline) goes straight to profiles/
+timeout 600 python bench.py --full > profiles/r03_bench_default.json
+tail -c 400 profiles/r03_bench_default.json

@@ -11,5 +11,6 @@ rm -rf gpurun_out/pmc_step_fetch gpurun_out/pmc_step_write
 bash tools/pmc_one.sh "5 fwd" "5 dgrad" "6 fwd" "7 fwd" "8 fwd" > /dev/null 2>&1
 for x in 5_fwd 5_dgrad 6_fwd 7_fwd 8_fwd; do echo "## layer $x"; python tools/pmc_summary.py gpurun_out/pc_$x; done > gpurun_out/r03_pmc_conv_box.md
 rm -rf gpurun_out/pc_*
-python bench.py > gpurun_out/r03_bench_default.json 2> gpurun_out/r03_bench_default.err
-tail -c 600 gpurun_out/r03_bench_default.json
+# the default bench line with everything --full adds (roofline, secondary legs, CPU baseline) goes straight to profiles/
+python bench.py --full > profiles/r03_bench_default.json
+tail -c 600 profiles/r03_bench_default.json

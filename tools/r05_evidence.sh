@@ -35,5 +35,6 @@ for L in "fwd 96 32 64" "dgrad 96 32 64" "fwd 48 64 128" "dgrad 48 64 128"; do
   rm -rf gpurun_out/pmc5s_${1}_${2}_*
 done
 rm -rf gpurun_out/pmc_step_fetch gpurun_out/pmc_step_write
-timeout 900 python bench.py > gpurun_out/r05_bench_default.json 2> gpurun_out/r05_bench_default.err
-tail -c 600 gpurun_out/r05_bench_default.json
+# the default bench line with everything --full adds (roofline, secondary legs, CPU baseline) goes straight to profiles/
+timeout 900 python bench.py --full > profiles/r05_bench_default.json
+tail -c 600 profiles/r05_bench_default.json

@@ -35,8 +35,9 @@ for L in "fwd 96 32 64" "dgrad 96 32 64" "fwd 48 64 128" "dgrad 48 64 128"; do
   rm -rf gpurun_out/pmc5s_${1}_${2}_*
 done
 rm -rf gpurun_out/pmc_step_fetch gpurun_out/pmc_step_write
-timeout 900 python bench.py > gpurun_out/r06_bench_default.json 2> gpurun_out/r06_bench_default.err
-tail -c 600 gpurun_out/r06_bench_default.json
+# the default bench line with everything --full adds (roofline, secondary legs, CPU baseline) goes straight to profiles/
+timeout 900 python bench.py --full > profiles/r06_bench_default.json
+tail -c 600 profiles/r06_bench_default.json
 
 # MedFormer (4 warm-up + 12 timed eager steps = 16 in the trace): kernel statistics of the eager step (the network R-Super trains)
 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_r06m -o r -- python tools/medformer_step.py 12 bf16 > /dev/null 2>&1

@@ -5,5 +5,6 @@ rm -rf gpurun_out/pmc_step_fetch gpurun_out/pmc_step_write
 timeout 600 bash tools/pmc_step.sh
 python tools/pmc_step_summary.py gpurun_out/pmc_step_fetch gpurun_out/pmc_step_write 6 r06 > gpurun_out/r06_pmc_step.md 2>&1; cp profiles/conv_traffic.json gpurun_out/conv_traffic.json
 rm -rf gpurun_out/pmc_step_fetch gpurun_out/pmc_step_write
-timeout 1500 python bench.py > gpurun_out/r06_bench_default.json 2> gpurun_out/r06_bench_default.err
-tail -c 400 gpurun_out/r06_bench_default.json
+# the default bench line with everything --full adds (roofline, secondary legs, CPU baseline) goes straight to profiles/
+timeout 1500 python bench.py --full > profiles/r06_bench_default.json
+tail -c 400 profiles/r06_bench_default.json
