@@ -482,6 +482,33 @@ int rsuper_zero_where(float* x, const uint8_t* m, long V, void* stream);
 int rsuper_count(const uint8_t* m, long V, unsigned int* count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Prediction post-processing and detection volumes -- predict_abdomenatlas.py, eval_AUC.py.  Volumes up to 2^31 voxels.
+ * No call issues a memset: every workspace is initialised by the call's own kernels, so stale contents do not matter.
+ * ------------------------------------------------------------------------------------------------ */
+/* eval_AUC.detection :56-112 for `planes` f32 volumes x[planes][Di][Hi][Wi]: ndimage.zoom(order=1) onto [Do][Ho][Wo] (f64 align-corners trilinear,
+ * input coordinate = o * (n_in - 1) / (n_out - 1); identity when the shapes agree), then for each of the nthr <= 255 thresholds (HOST array, sorted
+ * ascending, compared in f64 as `value > t`) the voxel count of binary_dilation(binary_erosion(B_t, box3), box3, iterations=2) & B_t -- computed as
+ * one integer pass: level L = #thresholds exceeded, final = min(max5(min3(L)), L) with min3 reading level 0 outside the volume, volume(t) =
+ * #(final > t).  erode == 0: #(L > t).  volumes: device [planes][nthr] i64; max_prob: device [planes] f64 = max of the resampled values.
+ * workspace: rsuper_detection_workspace_bytes(planes) bytes on the device. */
+long rsuper_detection_workspace_bytes(int planes);
+int rsuper_detection(const float* x, int planes, int Di, int Hi, int Wi, int Do, int Ho, int Wo, const double* thresholds, int nthr, int erode,
+                     long long* volumes, double* max_prob, void* workspace, void* stream);
+/* postprocess_npz :655-688 (--organ_mask_on_lesion) on pred[C][D][H][W]: out[k] = pred[lesion[k]] * binary_dilation(organ > 0.5, box3), organ =
+ * pred[organ_a[k]] (+ pred[organ_b[k]] when organ_b[k] >= 0).  u8: labels, the sum wraps as uint8; f32: probabilities, the sum is an f32 add.
+ * lesion / organ_a / organ_b: HOST arrays of n plane indices; out: device [n][D][H][W]. */
+int rsuper_organ_mask_u8(const uint8_t* pred, int C, int D, int H, int W, int n, const int* lesion, const int* organ_a, const int* organ_b,
+                         uint8_t* out, void* stream);
+int rsuper_organ_mask_f32(const float* pred, int C, int D, int H, int W, int n, const int* lesion, const int* organ_a, const int* organ_b,
+                          float* out, void* stream);
+/* keep_largest_component :692-716: out[D][H][W] (u8) = the largest face-connected component of mask > 0 (mask: u8 when is_u8, else f32); ties go to
+ * the component whose first voxel comes first in C order (SimpleITK's label order); an empty mask gives all ones (the reference's
+ * Equal(cc, 0)).  Union-find with the smallest linear index as root: tile labelling in LDS, atomicMin links across tiles, path compression,
+ * sizes, an atomicMax on (size << 32) | (0xFFFFFFFF - root).  workspace: rsuper_largest_component_workspace_bytes(D, H, W) bytes on the device. */
+long rsuper_largest_component_workspace_bytes(int D, int H, int W);
+int rsuper_largest_component(const void* mask, int is_u8, int D, int H, int W, uint8_t* out, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser -- train_ddp.py:352-357, training/utils.py:46-51,154-161.  host_* are HOST arrays of device pointers.
  * ------------------------------------------------------------------------------------------------ */
 /* *total_sq = sum of squared elements of the n gradient tensors (f64, deterministic order).  The accumulator need not be zeroed: the first launch

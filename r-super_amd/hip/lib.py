@@ -121,6 +121,12 @@ _SIGS = {
     'rsuper_plane_any_bits': (c_int, [P, c_int, c_int, c_int, c_long, P, P]),
     'rsuper_zero_where': (c_int, [P, P, c_long, P]),
     'rsuper_count': (c_int, [P, c_long, P, P]),
+    'rsuper_detection_workspace_bytes': (c_long, [c_int]),
+    'rsuper_detection': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P]),
+    'rsuper_organ_mask_u8': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    'rsuper_organ_mask_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    'rsuper_largest_component_workspace_bytes': (c_long, [c_int, c_int, c_int]),
+    'rsuper_largest_component': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

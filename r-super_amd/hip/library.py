@@ -14,6 +14,9 @@ loss ops (training/losses_foundation.py; reference call sites rsuper_train/train
     torch.ops.rsuper.plane_partials(logits, x_off, xstride, planes, kinv, t, k, w1, w2, kflags, tpk, tpk_classes) -> (sums of term 0, sums of the other terms)
     torch.ops.rsuper.seg_from_sums(sums, cw, B, C, V, scale) -> loss
     torch.ops.rsuper.dilate_volume(vol, kernel_size) -> vol      torch.ops.rsuper.ball_search(x, diameter, sigma) -> key   (no derivative: masks / indices)
+prediction post-processing (inference/detection.py, inference/postprocess.py; no derivative):
+    torch.ops.rsuper.detection_volumes(x, out_shape, thresholds, erode) -> (volumes, max_prob)
+    torch.ops.rsuper.organ_mask(pred, lesion, organ_a, organ_b) -> planes       torch.ops.rsuper.largest_component(mask) -> mask
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -146,3 +149,20 @@ def install_loss_ops(lf):
     _ops._dilate_volume_impl, _ops._ball_search_impl = _ops.dilate_volume, _ops.ball_search
     _ops.dilate_volume, _ops.ball_search = dv, bs
     lf._LIBRARY_INSTALLED = True
+
+
+_PP_OPS = None
+
+
+def install_postprocess_ops(detection_volumes, organ_mask, largest_component):
+    """Register the prediction post-processing operators of inference/detection.py and inference/postprocess.py (called at the end of
+    postprocess.py; idempotent) as plain CUDA kernels: integer volumes, masks and labels have no derivative."""
+    global _PP_OPS
+    if _PP_OPS is None:
+        _PP_OPS = (
+            _register_plain('detection_volumes', '(Tensor x, int[] out_shape, float[] thresholds, bool erode, Tensor? workspace=None) -> (Tensor, Tensor)',
+                            detection_volumes),
+            _register_plain('organ_mask', '(Tensor pred, int[] lesion, int[] organ_a, int[] organ_b) -> Tensor', organ_mask),
+            _register_plain('largest_component', '(Tensor mask, Tensor? workspace=None) -> Tensor', largest_component),
+        )
+    return _PP_OPS
