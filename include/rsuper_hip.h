@@ -75,6 +75,20 @@ int rsuper_conv3_variant(int v);
  * conv3d_wgrad_sv.hip), so that the tests can pin each tile-streaming kernel on small volumes.  t < 0 queries.  Returns the threshold in effect. */
 int rsuper_conv3_wgrad2_min_tiles(int t);
 
+/* THE dispatch query of rsuper_conv3_igemm: which kernel a launch runs, with which block width, writing how many statistics rows.  The library makes
+ * that choice in one function; this query, the three single-answer queries below and the launch itself all read it, so they cannot disagree.
+ *   bn = 0:  the library chooses the width (the depth-reuse kernel's where it takes the launch, else the volume-fitted kernel's, else the width that
+ *            fills the chip / pads least).  Pack the weights with plan[1] and pass it to rsuper_conv3_igemm.
+ *   bn != 0: the plan of a launch with that width.
+ *   N = 0 (D, H, W, epi ignored; bn = 0): a width query without a volume -- only plan[1] is meaningful.
+ *   Ca, Cb:  channels of the two sources (0, 0: unknown).  They only decide between kernels 1 and 2, which write the same rows.
+ *   src_flags bit 0: the launch has two sources of which exactly ONE carries (mean, rstd) (mra == NULL xor mrb == NULL); rsuper_conv3_igemm derives the
+ *            bit from its own arguments.  Kernels 2 and 3 stage both sources the same way and never take such a launch.
+ * plan[0] kernel: 0 classic, 1 producer/consumer, 2 weight-stationary, 3 depth-reuse, 4 volume-fitted K-split;  plan[1] bn;  plan[2] the volume-fitted
+ * kernel's box shape (else 0);  plan[3] its reduction splits (shape 3, needs Ca / Cb; else 0);  plan[4] rows per sample of `part`.
+ * The answer depends on rsuper_conv3_variant and on the workspace registered at the time (rsuper_conv3_set_workspace). */
+int rsuper_conv3_plan(int dtype, int epi, int N, int D, int H, int W, int Ca, int Cb, int n_cols, int src_flags, int bn, int* plan);
+
 /* Launches whose volume cannot fill the chip with 4x4x16-voxel tiles (the 24^3 / 12^3 levels of the UNet at batch 2:
  * model/dim3/unet.py:49-58 after three / four poolings) run a volume-fitted kernel under the default variant: boxes of
  * 4x4x8 or 4x4x4 voxels that divide the volume, GEMM rows = flat voxel index of the box, the block's four waves split the
@@ -86,10 +100,8 @@ int rsuper_conv3_box_bn(int dtype, int N, int D, int H, int W, int n_cols);
 /* The wide full-resolution layers (more than 32 columns, enough 4x8x16-voxel tiles for one persistent block per CU: up4.0 / the 96^3 level at
  * batch 2) run the depth-reuse kernel (conv3d_igemm_kd.hip: an activation fragment feeds the three kd taps, 0.5 / NF LDS fragment reads per MFMA):
  * returns the block width (64 forward; 64 / 96 / 128 data gradient) rsuper_conv3_igemm(dtype, epi, ..., n_cols, bn, N, D, H, W) takes that kernel
- * with -- pack the weights and size `part` with that bn -- else 0.
- * src_flags bit 0: the launch has two sources of which exactly ONE carries (mean, rstd) (mra == NULL xor mrb == NULL): the depth-reuse kernel stages
- * both sources the same way and does not take such a launch -- the query returns 0 and rsuper_conv3_igemm keeps the kernel that bn gets elsewhere.
- * rsuper_conv3_igemm derives the bit from its own arguments; pass the same value to this query and to rsuper_conv3_part_rows. */
+ * with, else 0 (rsuper_conv3_plan(..., bn = 0): kernel 3 and its width).  src_flags as for rsuper_conv3_plan: with bit 0 set the query returns 0 and
+ * rsuper_conv3_igemm keeps the kernel that bn gets elsewhere. */
 int rsuper_conv3_kd_bn(int dtype, int epi, int N, int D, int H, int W, int n_cols, int src_flags);
 
 /* Volumes of at most 6x6x6 voxels (the 6^3 bottleneck level: model/dim3/unet.py:53, four poolings of a 96^3 patch) run one box
@@ -102,8 +114,8 @@ int rsuper_conv3_set_workspace(void* ptr, size_t bytes);
 size_t rsuper_conv3_workspace_bytes(void);
 
 /* Rows per sample of the `part` buffer rsuper_conv3_igemm(dtype, epi, ..., n_cols, bn, N, D, H, W) writes under the
- * current variant (classic: one row per tile; producer/consumer: one row per (persistent block, consumer wave row)).
- * src_flags: as for rsuper_conv3_kd_bn (bit 0: one normalised + one raw source). */
+ * current variant (classic: one row per tile; producer/consumer: one row per (persistent block, consumer wave row)): plan[4] of
+ * rsuper_conv3_plan(..., bn).  src_flags as there (bit 0: one normalised + one raw source). */
 int rsuper_conv3_part_rows(int dtype, int epi, int N, int D, int H, int W, int n_cols, int bn, int src_flags);
 
 /* Implicit-GEMM convolution.  epi 0: forward  y = conv(prologue(x)) [+ res]; part <- per-tile (sum, sumsq) of y.
@@ -123,7 +135,7 @@ int rsuper_conv3_igemm(int dtype, int epi,
 /* The same launch with TWO output tensors: columns [0, out_split) go to `out`, columns [out_split, n_cols) to a tensor `out_part` ELEMENTS behind it (allocate
  * both from one buffer), each with row stride ldo.  For the fused [conv1 | shortcut] GEMM of a BasicBlock whose halves are narrower than a 128-byte line (32 bf16
  * channels: up4.0): every consumer of one half -- conv2's staging, its weight gradient, the ReLU mask of its data gradient, the InstanceNorm-backward tail -- then
- * reads whole lines instead of half-used ones.  out_split a multiple of 32; only launches the depth-reuse kernel takes (rsuper_conv3_kd_bn(...) == bn),
+ * reads whole lines instead of half-used ones.  out_split a multiple of 32; only launches the depth-reuse kernel takes (rsuper_conv3_plan: kernel 3),
  * RS_ERR_UNSUPPORTED otherwise: the caller falls back to the interleaved output. */
 int rsuper_conv3_igemm_split_out(int dtype, int epi,
                                  const void* xa, int lda, int Ca, const float* mra,

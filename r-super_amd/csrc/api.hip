@@ -20,6 +20,8 @@ static inline int ntiles_for(int n_cols, int bn) { const int per = bn / 32; retu
 static inline int pack_cols(int mode, int na, int nb) { return mode == 1 ? (nb ? (nb & 0xFFFF) : na) : na + nb; }
 static inline bool pack_range_ok(int mode, int na, int nb) { return mode != 1 || nb == 0 || ((nb >> 16) % 32 == 0 && (nb & 0xFFFF) > 0 && (nb >> 16) + (nb & 0xFFFF) <= na); }
 
+#include "igemm_plan.hpp"      // which kernel / block width / statistics rows a 3x3x3 igemm launch gets: igemm_plan, s2_kernel (needs dt_ok, bn_ok)
+
 // ---- optimiser: split the tensor list into kernel-argument sized chunks
 template <typename F>
 static int for_chunks(int n, void* const* p, void* const* g, void* const* m, void* const* v, void* const* e, const size_t* numel, F f) {
@@ -111,101 +113,30 @@ int rsuper_conv3_pack_weights_batch(int dtype, int n, const int* host_desc, cons
 
 int rsuper_conv3_tiles(int D, int H, int W) { return ((D + 3) / 4) * ((H + 3) / 4) * ((W + 15) / 16); }
 
-static int g_variant = 3;
 int rsuper_conv3_wgrad2_min_tiles(int t) { return rs_wgrad2_min_tiles(t); }
 
 int rsuper_conv3_variant(int v) {
     if (v >= 0 && v <= 8 && v != 5) g_variant = v;                   // 5 was the second-generation producer/consumer kernel (measured equal, removed)
     return g_variant;
 }
-// variant 2 (auto, default): producer/consumer kernel where it measured faster on MI355X -- data-gradient launches with
-// bn <= 64 (its epilogue operand prefetch), all 32-column launches, and small grids (persistent blocks fill the chip);
-// classic kernel elsewhere.
-// variant 3 (default): as variant 2, and 32-column launches over a single 32-channel K chunk (the 32 -> 32 layers at full
-// resolution) run the weight-stationary kernel (conv3d_igemm_ws.hip), which writes the same partial rows as the
-// producer/consumer kernel.  variant 4: weight-stationary kernel for every bf16 32-column launch (multi-chunk too; tests).
-static bool use_pc(int dtype, int epi, int bn, int tiles_total) {
-    if (dtype != RS_BF16) return false;
-    if (g_variant == 4) return bn == 32 || (bn <= 64 && (epi == 1 || tiles_total <= 1024));
-    if (g_variant == 2 || g_variant == 3) return bn <= 64 && (epi == 1 || bn == 32 || tiles_total <= 1024);
-    return g_variant == 1;
+int rsuper_conv3_plan(int dtype, int epi, int N, int D, int H, int W, int Ca, int Cb, int n_cols, int src_flags, int bn, int* plan) {
+    const IgemmPlan pl = igemm_plan(dtype, epi, N, D, H, W, Ca, Cb, n_cols, src_flags, bn);
+    if (!plan || pl.kernel < 0) return RS_ERR_ARG;
+    plan[0] = pl.kernel; plan[1] = pl.bn; plan[2] = pl.box_cfg; plan[3] = pl.nsplit; plan[4] = pl.part_rows;
+    return RS_OK;
 }
-
-// Volume-fitted K-split kernel (conv3d_igemm_box.hip) for launches that cannot fill the chip with 4x4x16-voxel tiles: bf16, more than
-// 32 columns, and fewer than 512 classic work items (the 24^3 / 12^3 / 6^3 levels at batch 2).  Shapes 1 / 2 (4x4x8 / 4x4x4 boxes) take
-// 64-column blocks; shape 3 (volumes of at most 6x6x6: one box per sample, the reduction split over blocks through the registered
-// workspace, second pass box_splitk_epilogue_kernel) takes 32-column blocks.  Variants 6 / 7 force the kernel for every bf16 launch
-// (6: shape chosen per volume, 7: the 4x4x4 box) -- test paths.
-// one registered workspace PER DEVICE (indexed by the current HIP device of the calling thread: a host that drives several GPUs from one process
-// registers one on each); launches on two streams of the same device share it and must not overlap 6^3-level convolutions
-static const int RS_MAX_DEVICES = 64;
-static void* g_ws_dev[RS_MAX_DEVICES] = {nullptr};
-static size_t g_ws_bytes_dev[RS_MAX_DEVICES] = {0};
-static int ws_dev() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= RS_MAX_DEVICES) return 0;
-    return d;
-}
-#define g_ws (g_ws_dev[ws_dev()])
-#define g_ws_bytes (g_ws_bytes_dev[ws_dev()])
-static const size_t BOXC_WS_BYTES = (size_t)256 * 216 * 32 * 4;    // nsplit x N x 216 x n_cols floats while N x ceil(n_cols / 32) <= 256 (rs_box_nsplit)
-// Bytes the split shape writes into the workspace: nsplit x N x voxels x n_cols floats.  rs_box_nsplit deals at most 256 / (N x groups) splits (at least
-// one), so beyond N x groups = 256 the requirement grows with N x n_cols without bound -- the shape is only taken while it fits what the caller registered.
-static size_t boxc_ws_need(int nsplit, int N, int D, int H, int W, int n_cols) {
-    return (size_t)nsplit * (size_t)N * (size_t)(D * H * W) * (size_t)n_cols * sizeof(float);
-}
-static bool boxc_fits(int N, int D, int H, int W, int n_cols) {
-    const int groups = (n_cols + 31) / 32;
-    const long ng = (long)N * groups;
-    const int smax = ng >= 256 ? 1 : (int)(256 / ng);
-    return g_ws && boxc_ws_need(smax, N, D, H, W, n_cols) <= g_ws_bytes;
-}
-static int box_shape(int dtype, int N, int D, int H, int W, int n_cols) {
-    if (dtype != RS_BF16) return 0;
-    const bool forced = g_variant == 6 || g_variant == 7;
-    static const int off = getenv("RSUPER_NO_BOX") ? atoi(getenv("RSUPER_NO_BOX")) : 0;      // 1: no box kernel, 2: no split shape
-    if (!forced && (g_variant != 3 || off == 1 || n_cols <= 32)) return 0;
-    if (g_variant != 7 && off != 2 && D <= 6 && H <= 6 && W <= 6 && boxc_fits(N, D, H, W, n_cols)) return 3;
-    if (g_variant == 7) return 2;
-    if (!forced && (long)N * rsuper_conv3_tiles(D, H, W) * ((n_cols + 127) / 128) >= 512) return 0;
-    return rs_box_config(N, D, H, W, n_cols);
-}
-static int box_for(int dtype, int bn, int N, int D, int H, int W, int n_cols) {
-    const int cfg = box_shape(dtype, N, D, H, W, n_cols);
-    return (cfg && bn == (cfg == 3 ? 32 : 64)) ? cfg : 0;
-}
-
-// Depth-reuse kernel (conv3d_igemm_kd.hip, round 5): bf16 launches with more than 32 columns whose volume gives the persistent blocks enough 4 x 8 x 16-voxel
-// tiles (the full-resolution level at batch 2: 3456 tiles; RSUPER_KD_MIN_TILES).  A pure function of (dtype, epi, shape, columns) so that the block width
-// (rsuper_conv3_kd_bn -> pick_bn), the partial-row count and the launch agree.  Forward launches (normalised sources, staging with arithmetic in registers)
-// take 64-column blocks; data-gradient launches (raw dY) 64 / 96 / 128.  Variant 8 forces it wherever its limits allow (tests).
-static int kd_bn_for(int dtype, int epi, int N, int D, int H, int W, int n_cols, int src_flags) {
-    if (dtype != RS_BF16 || n_cols <= 32) return 0;
-    if (src_flags & 1) return 0;        // one normalised and one raw source: the depth-reuse kernel stages both sources the same way (rs_igemm_kd_supported)
-    static const int off = getenv("RSUPER_KD") ? atoi(getenv("RSUPER_KD")) == 0 : 0;
-    static const int min_tiles = getenv("RSUPER_KD_MIN_TILES") ? atoi(getenv("RSUPER_KD_MIN_TILES")) : 400;
-    static const int dgrad = getenv("RSUPER_KD_DGRAD") ? atoi(getenv("RSUPER_KD_DGRAD")) : 0;
-    static const int wide = getenv("RSUPER_KD_WIDE") ? atoi(getenv("RSUPER_KD_WIDE")) : 0;
-    if (g_variant != 8 && (g_variant != 3 || off)) return 0;
-    if ((long)N * D * H * W >= (1l << 24) || D > 1023 || H > 1023 || W > 1023) return 0;
-    if (g_variant != 8) {
-        // measured (profiles/r05_conv_layers.txt, same box): forward launches of exactly 33 .. 64 columns at 96^3 / 48^3 gain 10-11 % (up4.0 648 -> 576 us,
-        // 64 -> 64 @48^3 60 -> 54 us); 128-column forwards (two column blocks) and the data gradients do not beat the 128-column classic / producer-consumer
-        // kernels yet -- they stay selectable (RSUPER_KD_DGRAD=1) and run every parity case under variant 8
-        const long tiles = (long)N * ((D + 3) / 4) * ((H + 7) / 8) * ((W + 15) / 16);
-        if (tiles < min_tiles) return 0;
-        if (epi == 0 && n_cols > 64) return 0;
-        if (epi == 1 && !dgrad) return 0;
-    }
-    // one column fragment per wave (64-column blocks): two fragments per wave (96 / 128-column blocks, raw sources by LDS-DMA) do not fit the register file
-    // without spills yet and measured slower (up4.0 data gradient: 96-column blocks 733 us against 705 us for 2 x 64); RSUPER_KD_WIDE=1 selects them
-    if (epi == 0 || !wide) return 64;
-    const int r = n_cols % 128;
-    return (n_cols > 128 || r == 0) ? 128 : r > 96 ? 128 : r > 64 ? 96 : 64;
-}
+// The earlier single-answer queries: thin readers of the plan (0 where the arguments describe no launch).
 int rsuper_conv3_kd_bn(int dtype, int epi, int N, int D, int H, int W, int n_cols, int src_flags) {
-    if (!dt_ok(dtype) || (epi != 0 && epi != 1) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || n_cols <= 0) return 0;
-    return kd_bn_for(dtype, epi, N, D, H, W, n_cols, src_flags);
+    const IgemmPlan pl = igemm_plan(dtype, epi, N, D, H, W, 0, 0, n_cols, src_flags, 0);
+    return pl.kernel == RS_IGEMM_KD ? pl.bn : 0;
+}
+int rsuper_conv3_box_bn(int dtype, int N, int D, int H, int W, int n_cols) {
+    // whatever the direction and the sources: the plan of a launch the depth-reuse kernel never takes (src_flags = 1)
+    const IgemmPlan pl = igemm_plan(dtype, 0, N, D, H, W, 0, 0, n_cols, 1, 0);
+    return pl.kernel == RS_IGEMM_BOX ? pl.bn : 0;
+}
+int rsuper_conv3_part_rows(int dtype, int epi, int N, int D, int H, int W, int n_cols, int bn, int src_flags) {
+    return bn ? igemm_plan(dtype, epi, N, D, H, W, 0, 0, n_cols, src_flags, bn).part_rows : 0;
 }
 
 int rsuper_conv3_set_workspace(void* ptr, size_t bytes) {
@@ -214,49 +145,12 @@ int rsuper_conv3_set_workspace(void* ptr, size_t bytes) {
 }
 size_t rsuper_conv3_workspace_bytes(void) { return BOXC_WS_BYTES; }
 
-int rsuper_conv3_box_bn(int dtype, int N, int D, int H, int W, int n_cols) {
-    const int cfg = box_shape(dtype, N, D, H, W, n_cols);
-    return cfg == 3 ? 32 : cfg ? 64 : 0;
-}
-
-int rsuper_conv3_part_rows(int dtype, int epi, int N, int D, int H, int W, int n_cols, int bn, int src_flags) {
-    if (bn == kd_bn_for(dtype, epi, N, D, H, W, n_cols, src_flags)) return rs_igemm_kd_part_rows(bn, N, D, H, W, n_cols);
-    if (const int cfg = box_for(dtype, bn, N, D, H, W, n_cols)) return rs_box_part_rows(cfg, D, H, W);
-    return rs_igemm_part_rows(bn, use_pc(dtype, epi, bn, N * rsuper_conv3_tiles(D, H, W)) ? 1 : 0, rsuper_conv3_tiles(D, H, W), n_cols, N);
-}
-
-// the persistent strided forward (conv3d_igemm_s2k.hip) takes bf16 forward GEMMs with a 16-channel-aligned source; RSUPER_S2K=0: the parity-class kernel everywhere
-static bool s2k_on() {                                                       // read per call (tests switch it inside one process)
-    const char* e = getenv("RSUPER_S2K");
-    return !(e && atoi(e) == 0);
-}
-static bool s2d_on() {                                                       // RSUPER_S2D=0: the parity-class data gradient
-    const char* e = getenv("RSUPER_S2D");
-    return !(e && atoi(e) == 0);
-}
-static IgemmParams s2_shape(int n_cols, int Ca, int Cb, int N, int FD, int FH, int FW) {
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.ntiles = ntiles_for(n_cols, 64); p.bn = 64;
-    p.N = N; p.D = (FD + 1) / 2; p.H = (FH + 1) / 2; p.W = (FW + 1) / 2; p.Cout = n_cols;
-    p.a.C = Ca; p.b.C = Cb;
-    return p;
-}
 int rsuper_conv3_s2_part_rows(int dtype, int mode, int Ca, int Cb, int n_cols, int N, int FD, int FH, int FW) {
     if ((mode != 1 && mode != 2) || FD <= 0 || FH <= 0 || FW <= 0 || N <= 0 || n_cols <= 0) return 0;
     const int OD = (FD + 1) / 2, OH = (FH + 1) / 2, OW = (FW + 1) / 2, td = mode == 2 ? 2 : 4;
-    if (mode == 1 && s2k_on()) {
-        IgemmParams p = s2_shape(n_cols, Ca, Cb, N, FD, FH, FW);
-        static const float one = 1.f;
-        p.a.mr = &one;                                                       // "normalised source" for the support query
-        if (rs_igemm_s2k_supported(p, dtype, FD, FH, FW)) return rs_igemm_s2k_part_rows(p.ntiles, n_cols, N, OD, OH, OW);
-    }
-    if (mode == 2 && s2d_on()) {
-        IgemmParams p = s2_shape(n_cols, Ca, Cb, N, FD, FH, FW);
-        static const float one = 1.f;
-        p.ea.mr = &one; p.ea.x = &one;
-        if (rs_igemm_s2d_supported(p, dtype, FD, FH, FW)) return rs_igemm_s2d_part_rows(n_cols, N, OD, OH, OW);
-    }
+    const S2Kernel k = s2_kernel(dtype, mode, Ca, Cb, n_cols, N, FD, FH, FW);
+    if (k == S2_S2K) return rs_igemm_s2k_part_rows(ntiles_for(n_cols, 64), n_cols, N, OD, OH, OW);
+    if (k == S2_S2D) return rs_igemm_s2d_part_rows(n_cols, N, OD, OH, OW);
     return ((OD + td - 1) / td) * ((OH + 3) / 4) * ((OW + 15) / 16);
 }
 // Stride-2 forward (mode 1) / its data gradient (mode 2) on the parity-class kernel (conv3d_igemm_s2.hip); 64-column blocks
@@ -282,8 +176,10 @@ int rsuper_conv3_igemm_s2(int dtype, int mode, const void* xa, int lda, int Ca, 
     p.N = N; p.D = (FD + 1) / 2; p.H = (FH + 1) / 2; p.W = (FW + 1) / 2; p.Cout = n_cols;
     p.out = out; p.ldo = ldo; p.part = part;
     p.ea = {exa, elda, n_cols, emra};
-    if (mode == 1 && s2k_on() && rs_igemm_s2k_supported(p, dtype, FD, FH, FW)) return rs_launch_igemm_s2k(p, FD, FH, FW, ST(stream));
-    if (mode == 2 && s2d_on() && rs_igemm_s2d_supported(p, dtype, FD, FH, FW)) return rs_launch_igemm_s2d(p, FD, FH, FW, ST(stream));
+    // the argument checks above leave the strided kernels nothing to refuse beyond the shape: one normalised source (mode 1), raw dy + a normalised input (mode 2)
+    const S2Kernel k = s2_kernel(dtype, mode, Ca, p.b.C, n_cols, N, FD, FH, FW);
+    if (k == S2_S2K) return rs_launch_igemm_s2k(p, FD, FH, FW, ST(stream));
+    if (k == S2_S2D) return rs_launch_igemm_s2d(p, FD, FH, FW, ST(stream));
     return rs_launch_igemm_s2(p, dtype, mode, FD, FH, FW, ST(stream));
 }
 
@@ -319,20 +215,17 @@ static int conv3_igemm_impl(int dtype, int epi, const void* xa, int lda, int Ca,
     p.out = out; p.ldo = ldo; p.res = res; p.ldr = ldr; p.part = part;
     p.ea = {exa, elda, eCa, emra};
     p.eb = {exb, eldb, eCb, emrb};
-    p.box = box_for(dtype, bn, N, D, H, W, n_cols);
-    if (p.box == 3) {
-        p.ws = (float*)g_ws; p.nsplit = rs_box_nsplit(N, n_cols, (Ca + 31) / 32 + (Cb + 31) / 32);
+    // one normalised + one raw source: the plan keeps such a launch off the kernels that stage both sources the same way
+    const int src_flags = (Cb > 0 && (mra != nullptr) != (mrb != nullptr)) ? 1 : 0;
+    const IgemmPlan pl = igemm_plan(dtype, epi, N, D, H, W, Ca, p.b.C, n_cols, src_flags, bn);
+    p.kernel = pl.kernel; p.box = pl.box_cfg;
+    if (pl.box_cfg == 3) {
+        p.ws = (float*)g_ws; p.nsplit = pl.nsplit;
         if (!g_ws || boxc_ws_need(p.nsplit, N, D, H, W, n_cols) > g_ws_bytes) return RS_ERR_ARG;      // never write past the registered workspace
     }
-    p.pc = use_pc(dtype, epi, bn, N * rsuper_conv3_tiles(D, H, W)) ? 1 : 0;
-    // the depth-reuse kernel is selected from the shape AND the sources of this launch: a launch it cannot take (one normalised + one raw
-    // source) keeps the kernel the same bn gets everywhere else, and rsuper_conv3_part_rows(..., src_flags = 1) sizes `part` for that kernel
-    const int src_flags = (Cb > 0 && (mra != nullptr) != (mrb != nullptr)) ? 1 : 0;
-    if (bn == kd_bn_for(dtype, epi, N, D, H, W, n_cols, src_flags)) { p.pc = 3; p.box = 0; }
-    else if (bn == 96) return RS_ERR_UNSUPPORTED;                  // 96-column blocks exist on the depth-reuse kernel only
-    if (p.pc && bn == 32 && (g_variant == 4 || (g_variant == 3 && (Ca + 31) / 32 + (Cb + 31) / 32 == 1))) p.pc = 2;
+    if (bn == 96 && pl.kernel != RS_IGEMM_KD) return RS_ERR_UNSUPPORTED;                            // 96-column blocks exist on the depth-reuse kernel only
     if (out_split) {
-        if (p.pc != 3 || !rs_igemm_kd_supported(p, dtype)) return RS_ERR_UNSUPPORTED;      // the split store exists in the depth-reuse kernel's epilogue only
+        if (pl.kernel != RS_IGEMM_KD || !rs_igemm_kd_supported(p, dtype)) return RS_ERR_UNSUPPORTED;  // the split store exists in the depth-reuse kernel's epilogue only
         p.out_split = out_split; p.out_part = out_part;
     }
     return rs_launch_igemm(p, dtype, epi, ST(stream));

@@ -887,27 +887,32 @@ __global__ __launch_bounds__(256) void pack_tile_kernel(PackBatch b, T* out) {
 
 }  // namespace
 
-int rs_igemm_part_rows(int bn, int pc, int tiles, int n_cols, int N) {
-    if (!pc) return tiles;                                            // classic kernel: one row per tile
-    const int gy = (n_cols + bn - 1) / bn;                            // producer/consumer: one row per (persistent block, wm)
+int rs_igemm_part_rows(int bn, bool persistent, int tiles, int n_cols, int N) {
+    if (!persistent) return tiles;                                    // classic kernel: one row per tile
+    const int gy = (n_cols + bn - 1) / bn;                            // producer/consumer, weight-stationary: one row per (persistent block, wm)
     return pc_grid_x(tiles, gy, N) * (bn == 32 ? 4 : 2);
 }
 
+// p.kernel is igemm_plan's choice (igemm_plan.hpp).  A kernel that cannot take the launch for a reason the plan does not see (row strides, packed tiles that are
+// not a multiple of bn / 32) refuses it: no case falls through to another kernel, `part` is sized for the one the plan names.
 int rs_launch_igemm(const IgemmParams& p, int dtype, int epi, hipStream_t st) {
-    if (p.box > 0 && dtype == RS_BF16) return rs_launch_igemm_box(p, p.box, epi, st);
-    if (p.pc == 3) return rs_igemm_kd_supported(p, dtype) ? rs_launch_igemm_kd(p, epi, st) : RS_ERR_UNSUPPORTED;
-    if (p.pc == 2 && rs_igemm_ws_supported(p, dtype, epi)) return rs_launch_igemm_ws(p, epi, st);
-    if (dtype == RS_BF16 && p.pc) {
-        if (p.ntiles % (p.bn / 32)) return RS_ERR_ARG;
-        switch (p.bn) {
-            case 32: return launch_pc<bf16_t, 4, 2, 1, 1>(p, epi, st);
-            case 64: return launch_pc<bf16_t, 2, 4, 2, 1>(p, epi, st);
-            case 128: return launch_pc<bf16_t, 2, 4, 2, 2>(p, epi, st);
-        }
-        return RS_ERR_ARG;
+    switch (p.kernel) {
+        case RS_IGEMM_BOX: return dtype == RS_BF16 && p.box > 0 ? rs_launch_igemm_box(p, p.box, epi, st) : RS_ERR_ARG;
+        case RS_IGEMM_KD: return rs_igemm_kd_supported(p, dtype) ? rs_launch_igemm_kd(p, epi, st) : RS_ERR_UNSUPPORTED;
+        case RS_IGEMM_WS: return rs_igemm_ws_supported(p, dtype) ? rs_launch_igemm_ws(p, epi, st) : RS_ERR_UNSUPPORTED;
+        case RS_IGEMM_PC:
+            if (dtype != RS_BF16 || p.ntiles % (p.bn / 32)) return RS_ERR_ARG;
+            switch (p.bn) {
+                case 32: return launch_pc<bf16_t, 4, 2, 1, 1>(p, epi, st);
+                case 64: return launch_pc<bf16_t, 2, 4, 2, 1>(p, epi, st);
+                case 128: return launch_pc<bf16_t, 2, 4, 2, 2>(p, epi, st);
+            }
+            return RS_ERR_ARG;
+        case RS_IGEMM_CLASSIC:
+            if (dtype == RS_F32) return launch_dt<float>(p, epi, st);
+            if (dtype == RS_BF16) return launch_dt<bf16_t>(p, epi, st);
+            return RS_ERR_ARG;
     }
-    if (dtype == RS_F32) return launch_dt<float>(p, epi, st);
-    if (dtype == RS_BF16) return launch_dt<bf16_t>(p, epi, st);
     return RS_ERR_ARG;
 }
 

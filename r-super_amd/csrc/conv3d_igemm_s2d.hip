@@ -376,14 +376,15 @@ size_t s2d_smem(int tiles, int gx) { return 2 * (size_t)HB + 256 + NW * (size_t)
 
 }  // namespace
 
-// data gradient, bf16, raw dy sources whose channels are multiples of 16; p.Cout = the forward input's channels
-bool rs_igemm_s2d_supported(const IgemmParams& p, int dtype, int FD, int FH, int FW) {
-    if (dtype != RS_BF16 || p.a.mr || p.b.mr || !p.ea.mr || !p.ea.x) return false;
-    if ((p.a.C % 16) || (p.b.C % 16) || p.a.C < 16) return false;
-    if (p.D > 1020 || p.H > 1020 || p.W > 4000) return false;
-    if ((unsigned long long)p.N * FD * FH * FW >= (1ull << 24)) return false;     // __umul24 of the voxel index: the data gradient writes and masks on the FULL grid
-    const int tiles = s2d_tiles(p.D, p.H, p.W), gy = (p.Cout + 31) / 32;
-    return s2d_smem(tiles, s2d_grid_x(tiles, gy, p.N)) <= 160 * 1024 && gy <= p.ntiles;
+// data gradient, bf16, (raw) dy sources whose channels are multiples of 16; n_cols = the forward input's channels
+bool rs_igemm_s2d_shape_ok(int dtype, int Ca, int Cb, int n_cols, int N, int FD, int FH, int FW) {
+    const int D = (FD + 1) / 2, H = (FH + 1) / 2, W = (FW + 1) / 2;
+    if (dtype != RS_BF16) return false;
+    if ((Ca % 16) || (Cb % 16) || Ca < 16) return false;
+    if (D > 1020 || H > 1020 || W > 4000) return false;
+    if ((unsigned long long)N * FD * FH * FW >= (1ull << 24)) return false;     // __umul24 of the voxel index: the data gradient writes and masks on the FULL grid
+    const int tiles = s2d_tiles(D, H, W), gy = (n_cols + 31) / 32;
+    return s2d_smem(tiles, s2d_grid_x(tiles, gy, N)) <= 160 * 1024;              // gy <= the packed 32-column tiles: the weights are packed for 64-column blocks
 }
 
 int rs_igemm_s2d_part_rows(int n_cols, int N, int D, int H, int W) {

@@ -409,18 +409,19 @@ int launch_s2k(const IgemmParams& p, int FD, int FH, int FW, hipStream_t st) {
 
 }  // namespace
 
-// forward, bf16, one normalised source whose channels are a multiple of 16, even half-grid-independent full-resolution sizes are NOT required
-bool rs_igemm_s2k_supported(const IgemmParams& p, int dtype, int FD, int FH, int FW) {
-    if (dtype != RS_BF16 || !p.a.mr || p.b.C != 0 || p.res) return false;
-    if ((p.a.C % 16) || p.a.C < 16 || p.a.C > 512) return false;
-    if (p.D > 1020 || p.H > 1020 || p.W > 4000) return false;
-    if ((unsigned long long)p.N * FD * FH * FW >= (1ull << 24)) return false;   // __umul24 of the voxel index
-    const int ncf = s2k_ncf(p.Cout);
-    const int tiles = s2k_tiles(ncf, p.D, p.H, p.W);
-    const int gy = (p.ntiles + ncf - 1) / ncf;
-    const int gx = s2k_grid_x(tiles, gy, p.N);
+// forward, bf16, one (normalised) source whose channels are a multiple of 16, even half-grid-independent full-resolution sizes are NOT required
+bool rs_igemm_s2k_shape_ok(int dtype, int Ca, int Cb, int n_cols, int N, int FD, int FH, int FW) {
+    const int D = (FD + 1) / 2, H = (FH + 1) / 2, W = (FW + 1) / 2;
+    if (dtype != RS_BF16 || Cb != 0) return false;
+    if ((Ca % 16) || Ca < 16 || Ca > 512) return false;
+    if (D > 1020 || H > 1020 || W > 4000) return false;
+    if ((unsigned long long)N * FD * FH * FW >= (1ull << 24)) return false;   // __umul24 of the voxel index
+    const int ncf = s2k_ncf(n_cols), ntiles = ((n_cols + 63) / 64) * 2;       // 64-column blocks
+    const int tiles = s2k_tiles(ncf, D, H, W);
+    const int gy = (ntiles + ncf - 1) / ncf;
+    const int gx = s2k_grid_x(tiles, gy, N);
     const size_t hb = ncf == 4 ? Geo<4>::HB : Geo<8>::HB;
-    return 2 * hb + (size_t)p.a.C * 8 + NW * (size_t)SCR_BYTES + ((tiles + gx - 1) / gx + 4) * 16 <= 160 * 1024;
+    return 2 * hb + (size_t)Ca * 8 + NW * (size_t)SCR_BYTES + ((tiles + gx - 1) / gx + 4) * 16 <= 160 * 1024;
 }
 
 int rs_igemm_s2k_part_rows(int ntiles, int n_cols, int N, int D, int H, int W) {

@@ -531,12 +531,10 @@ int launch_ws(const IgemmParams& p, int epi, hipStream_t st) {
 }  // namespace
 
 // Weight-stationary kernel: bf16, bn 32, both sources normalised (forward) or both raw (data gradient).
-bool rs_igemm_ws_supported(const IgemmParams& p, int dtype, int epi) {
+bool rs_igemm_ws_supported(const IgemmParams& p, int dtype) {
     if (dtype != RS_BF16 || p.bn != 32) return false;
     const bool na = p.a.mr != nullptr, nb = p.b.C > 0 ? p.b.mr != nullptr : na;
-    if (na != nb) return false;
-    (void)epi;
-    return true;
+    return na == nb;
 }
 
 int rs_launch_igemm_ws(const IgemmParams& p, int epi, hipStream_t st) {

@@ -12,6 +12,15 @@ struct ConvSrc {
     const float* mr;   // [N][C][2] (mean, rstd) -> fused InstanceNorm+ReLU prologue; nullptr -> raw
 };
 
+// The kernels of the stride-1 3x3x3 implicit GEMM.  igemm_plan (igemm_plan.hpp) is the only place one is chosen; rs_launch_igemm switches over it.
+enum IgemmKernel {
+    RS_IGEMM_CLASSIC = 0,  // one block per tile (conv3d_igemm.hip; f32 and bf16)
+    RS_IGEMM_PC = 1,       // producer/consumer persistent kernel (bf16)
+    RS_IGEMM_WS = 2,       // weight-stationary kernel (bf16, bn 32)
+    RS_IGEMM_KD = 3,       // depth-reuse kernel (bf16, bn 64 / 96 / 128)
+    RS_IGEMM_BOX = 4       // volume-fitted K-split kernel (bf16; shape in IgemmParams::box)
+};
+
 struct IgemmParams {
     ConvSrc a, b;          // GEMM-K sources (b.C == 0 when unused)
     const void* wp;        // packed B fragments (rs_launch_pack)
@@ -22,9 +31,9 @@ struct IgemmParams {
     void* out; int ldo;
     const void* res; int ldr;   // EPI 0: optional residual added before store
     float* part;           // per-block partial sums [N][rows][Cout][2] or nullptr (rows = rs_igemm_part_rows)
-    int pc;                // 1: producer/consumer persistent kernel (bf16); 2: weight-stationary kernel (bf16, bn 32); 3: depth-reuse kernel (bf16, bn 64 / 96 / 128)
+    int kernel;            // IgemmKernel (host dispatch only: no kernel reads it)
     ConvSrc ea, eb;        // EPI 1: forward inputs (with mr) whose relu mask / x_n the data-gradient needs
-    int box;               // > 0: volume-fitted K-split kernel (conv3d_igemm_box.hip), value = rs_box_config (3: one box per sample, reduction split over blocks)
+    int box;               // RS_IGEMM_BOX: the box shape, rs_box_config (3: one box per sample, reduction split over blocks); 0 otherwise
     float* ws; int nsplit; // box == 3: f32 workspace [nsplit][N * D * H * W][Cout] and the number of chunk ranges
     int out_split; long long out_part;   // out_split > 0 (depth-reuse kernel only): columns >= out_split go to a second tensor `out_part` ELEMENTS behind `out`, both with row stride ldo
 };
@@ -55,9 +64,9 @@ struct PackBatch {
 };
 int rs_launch_pack_batch(PackBatch& b, int dtype, void* out, hipStream_t st);
 int rs_launch_igemm(const IgemmParams& p, int dtype, int epi, hipStream_t st);
-int rs_igemm_part_rows(int bn, int pc, int tiles, int n_cols, int N);
-// weight-stationary variant (conv3d_igemm_ws.hip): bf16, bn 32 / 64; same partial-row count as the producer/consumer kernel
-bool rs_igemm_ws_supported(const IgemmParams& p, int dtype, int epi);
+int rs_igemm_part_rows(int bn, bool persistent, int tiles, int n_cols, int N);     // classic / (producer/consumer and weight-stationary) kernels
+// weight-stationary variant (conv3d_igemm_ws.hip): bf16, bn 32, both sources normalised or both raw; same partial-row count as the producer/consumer kernel
+bool rs_igemm_ws_supported(const IgemmParams& p, int dtype);
 int rs_launch_igemm_ws(const IgemmParams& p, int epi, hipStream_t st);
 // depth-reuse kernel for the wide full-resolution layers (conv3d_igemm_kd.hip): bf16, 64 / 96 / 128-column blocks, 4 x 8 x 16-voxel tiles
 bool rs_igemm_kd_supported(const IgemmParams& p, int dtype);
@@ -70,12 +79,13 @@ int rs_box_nsplit(int N, int n_cols, int nch);
 int rs_launch_igemm_box(const IgemmParams& p, int cfg, int epi, hipStream_t st);
 // stride-2 forward (mode 1) / data gradient (mode 2) by parity classes (conv3d_igemm_s2.hip): p.D/H/W = half-resolution grid, bn 64
 int rs_launch_igemm_s2(const IgemmParams& p, int dtype, int mode, int FD, int FH, int FW, hipStream_t st);
-// persistent strided forward (conv3d_igemm_s2k.hip): bf16, one normalised source; statistics rows = rs_igemm_s2k_part_rows per sample
-bool rs_igemm_s2k_supported(const IgemmParams& p, int dtype, int FD, int FH, int FW);
+// persistent strided forward (conv3d_igemm_s2k.hip): bf16, one normalised source; statistics rows = rs_igemm_s2k_part_rows per sample.
+// *_shape_ok: everything the kernel requires of a launch that rsuper_conv3_igemm_s2's own argument checks do not already guarantee
+bool rs_igemm_s2k_shape_ok(int dtype, int Ca, int Cb, int n_cols, int N, int FD, int FH, int FW);
 int rs_igemm_s2k_part_rows(int ntiles, int n_cols, int N, int D, int H, int W);
 int rs_launch_igemm_s2k(const IgemmParams& p, int FD, int FH, int FW, hipStream_t st);
 // persistent strided data gradient (conv3d_igemm_s2d.hip): bf16, raw dy sources; InstanceNorm-backward rows = rs_igemm_s2d_part_rows per sample
-bool rs_igemm_s2d_supported(const IgemmParams& p, int dtype, int FD, int FH, int FW);
+bool rs_igemm_s2d_shape_ok(int dtype, int Ca, int Cb, int n_cols, int N, int FD, int FH, int FW);
 int rs_igemm_s2d_part_rows(int n_cols, int N, int D, int H, int W);
 int rs_launch_igemm_s2d(const IgemmParams& p, int FD, int FH, int FW, hipStream_t st);
 size_t rs_packed_elems(int dtype, int ka, int kb, int ntiles);

@@ -23,6 +23,7 @@ _SIGS = {
     'rsuper_conv3_tiles': (c_int, [c_int] * 3),
     'rsuper_conv3_variant': (c_int, [c_int]),
     'rsuper_conv3_wgrad2_min_tiles': (c_int, [c_int]),
+    'rsuper_conv3_plan': (c_int, [c_int] * 11 + [P]),
     'rsuper_conv3_box_bn': (c_int, [c_int] * 6),
     'rsuper_conv3_kd_bn': (c_int, [c_int] * 8),
     'rsuper_conv3_set_workspace': (c_int, [P, c_size_t]),
@@ -132,6 +133,9 @@ _SIGS = {
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),
     'rsuper_adamw_ema_step_dyn': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P, P, P]),
 }
+
+# plan[0] of rsuper_conv3_plan
+IGEMM_CLASSIC, IGEMM_PC, IGEMM_WS, IGEMM_KD, IGEMM_BOX = range(5)
 
 ERR = {1: 'RSUPER_ERR_ARG', 2: 'RSUPER_ERR_LAUNCH', 3: 'RSUPER_ERR_UNSUPPORTED', 4: 'RSUPER_ERR_NO_DEVICE'}
 

@@ -5,6 +5,7 @@ Activation convention between functions: a contiguous tensor of shape (N, D, H, 
 bf16 or f32) plus its InstanceNorm statistics `mr` of shape (N, C, 2) = (mean, rstd), f32, computed by the
 producing kernel's epilogue (model/dim3/conv_layers.py:40-42: eps=1e-4, affine=False, biased variance).
 """
+import ctypes
 import os
 
 import torch
@@ -55,46 +56,24 @@ def _L():
     return L
 
 
+def igemm_plan(dtype, epi, dims, n_cols, bn=0, mixed=False, Ca=0, Cb=0):
+    """rsuper_conv3_plan: (kernel, bn, box shape, reduction splits, rows of `part`) of one stride-1 3x3x3 launch -- the library's single dispatch decision.
+    bn = 0: the library chooses the width.  dims = (N, D, H, W), or None for a width query without a volume.  epi 0 forward, 1 data gradient.
+    mixed: the launch has one normalised and one raw source.  Ca, Cb (optional) only tell the weight-stationary kernel from the producer/consumer one."""
+    out = (ctypes.c_int * 5)()
+    _l.check(_L().rsuper_conv3_plan(_DT[dtype], epi, *(dims if dims is not None else (0, 0, 0, 0)), Ca, Cb, n_cols, 1 if mixed else 0, bn, out), 'conv3_plan')
+    return tuple(out)
+
+
 def pick_bn(n_cols, dtype, tiles_total=None, dims=None, epi=None, mixed=False):
-    """Block N tile of the implicit GEMM (32/64/128 output columns); f32 parity mode is limited to 64.
-    tiles_total (spatial tiles x batch): on small volumes prefer the largest tile that still yields >= 512 workgroups
-    (24^3 and below would otherwise leave most of the 256 CUs idle; the narrower tiles also run on the persistent kernel).
-    dims = (N, D, H, W): launches the library would hand to the volume-fitted K-split kernel (rsuper_conv3_box_bn: low-resolution
-    levels that cannot fill the chip with 4x4x16 tiles) take its 64-column blocks.
-    epi (0 forward, 1 data gradient; with dims): launches the library hands to the depth-reuse kernel (rsuper_conv3_kd_bn: the wide full-resolution
-    layers) take its 64 / 96 / 128-column blocks.  mixed: the launch has one normalised and one raw source (the depth-reuse kernel does not take those;
-    pass the same flag to part_buffer)."""
-    cands = (32, 64) if dtype == torch.float32 else (32, 64, 128)
-    if dims is not None and epi is not None and dtype != torch.float32:
-        bn = _L().rsuper_conv3_kd_bn(_DT[dtype], epi, *dims, n_cols, 1 if mixed else 0)
-        if bn:
-            return bn
-    if dtype != torch.float32 and dims is None and _L().rsuper_conv3_variant(-1) in (6, 7):
-        return 64         # forced volume-fitted kernel (tests): 64-column blocks whatever the column count
-    if dims is not None and dtype != torch.float32:
-        bn = _L().rsuper_conv3_box_bn(_DT[dtype], *dims, n_cols)
-        if bn:
-            return bn
-    if n_cols <= 32:
-        return 32
-    if dtype != torch.float32 and _L().rsuper_conv3_variant(-1) == 4:
-        return 32         # forced weight-stationary kernel (tests / experiments): 32-column blocks, Cout / 32 of them in grid.y
-    fill = int(os.environ.get('RSUPER_BN_FILL', '512'))       # two resident blocks per CU (measured 128 / 256 / 512: 13.89 / - / 13.80 ms per step)
-    if tiles_total is not None and tiles_total * -(-n_cols // 128) < fill:
-        for bn in reversed(cands):
-            if tiles_total * -(-n_cols // bn) >= fill:
-                return bn
-        return 32
-    if dtype != torch.float32 and n_cols > 64 and n_cols % 64:
-        return 32         # e.g. 96 columns (up4.0 data gradient): three exact 32-column tiles on the producer/consumer kernel
-                          # (671 us) beat one 25 %-padded 128 tile on the classic kernel (739 us)        # e.g. 96 columns: one padded 128 tile beats three 32-column tap-split tiles
-    best = None
-    for bn in cands:
-        padded = -(-n_cols // bn) * bn
-        key = (padded, -bn)
-        if best is None or key < best[0]:
-            best = (key, bn)
-    return best[1]
+    """Block N tile of the implicit GEMM (32 / 64 / 96 / 128 output columns; f32 parity mode is limited to 64) the library chooses for a launch: igemm_plan with
+    bn = 0.  epi not given counts as a forward launch.  The library derives the tile count from dims; a caller that gives the volume WITHOUT tiles_total
+    (direct kernel tests) keeps the width chosen for a chip that the launch fills, wherever neither the depth-reuse nor the volume-fitted kernel sets one."""
+    assert dims is not None or tiles_total is None, 'a tile count without the volume it belongs to'
+    kernel, bn = igemm_plan(dtype, epi or 0, dims, n_cols, mixed=mixed)[:2]
+    if dims is not None and tiles_total is None and kernel not in (_l.IGEMM_KD, _l.IGEMM_BOX):
+        return igemm_plan(dtype, 0, None, n_cols)[1]
+    return bn
 
 
 def _chk_act(x):
@@ -103,11 +82,10 @@ def _chk_act(x):
 
 def part_buffer(dtype, dims, n_cols, bn, device, fill=None, epi=0, mixed=False):
     """Per-block partial-sum buffer (N, rows, n_cols, 2) in the shape rsuper_conv3_igemm(epi, ...) writes for this dtype/bn."""
-    N, D, H, W = dims
-    rows = _L().rsuper_conv3_part_rows(_DT[dtype], epi, N, D, H, W, n_cols, bn, 1 if mixed else 0)
+    shape = (dims[0], igemm_plan(dtype, epi, dims, n_cols, bn, mixed)[4], n_cols, 2)
     if fill is None:
-        return torch.empty((N, rows, n_cols, 2), device=device, dtype=torch.float32)
-    return torch.full((N, rows, n_cols, 2), fill, device=device, dtype=torch.float32)
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    return torch.full(shape, fill, device=device, dtype=torch.float32)
 
 
 def stats_finalize(part, cnt, mode=0, split=0):
@@ -134,68 +112,64 @@ def _spec_cols(sp):
     return (sp[6] & 0xFFFF) if (sp[0] == 1 and sp[6]) else sp[5] + sp[6]
 
 
-def pack_weights_batch(dtype, specs):
-    """One launch for many layers.  specs: list of (mode, wa, wb, ka, kb, na, nb, bn).  Returns a list of packed views."""
-    import ctypes
+def _pack_desc(dtype, specs):
+    """The host side of one rsuper_conv3_pack_weights_batch launch: (dt, n, desc, wa, wb, oe) ctypes arguments and the element offsets of the n buffers."""
     dt = _DT[dtype]
     n = len(specs)
-    sizes = [_L().rsuper_conv3_packed_elems(dt, sp[3], sp[4], _spec_cols(sp), sp[7]) for sp in specs]
     offs = [0]
-    for z in sizes:
-        offs.append(offs[-1] + z)
-    buf = torch.empty((offs[-1],), device=specs[0][1].device, dtype=dtype)
+    for sp in specs:
+        offs.append(offs[-1] + _L().rsuper_conv3_packed_elems(dt, sp[3], sp[4], _spec_cols(sp), sp[7]))
     desc = (ctypes.c_int * (6 * n))(*[v for sp in specs for v in (sp[0], sp[3], sp[4], sp[5], sp[6], sp[7])])
     wa = (ctypes.c_void_p * n)(*[sp[1].data_ptr() for sp in specs])
     wb = (ctypes.c_void_p * n)(*[(sp[2].data_ptr() if sp[2] is not None else None) for sp in specs])
     oe = (ctypes.c_size_t * n)(*offs[:-1])
-    _l.check(_L().rsuper_conv3_pack_weights_batch(dt, n, desc, wa, wb, oe, _ptr(buf), _stream()), 'pack_weights_batch')
-    return [buf[offs[i]:offs[i + 1]] for i in range(n)]
+    return (dt, n, desc, wa, wb, oe), offs
+
+
+def _pack_launch(args, offs, dtype, device):
+    buf = torch.empty((offs[-1],), device=device, dtype=dtype)
+    _l.check(_L().rsuper_conv3_pack_weights_batch(*args, _ptr(buf), _stream()), 'pack_weights_batch')
+    return [buf[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+
+
+def pack_weights_batch(dtype, specs):
+    """One launch for many layers.  specs: list of (mode, wa, wb, ka, kb, na, nb, bn).  Returns a list of packed views."""
+    return _pack_launch(*_pack_desc(dtype, specs), dtype, specs[0][1].device)
 
 
 _BLOCK_PACK_CACHE = {}
 
 
-def block_packs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims):
+def block_packs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims, mixed=False):
     """block_pack_specs + pack_weights_batch for one BasicBlock, with the launch descriptor (tile sizes, offsets, ctypes argument arrays) cached per
     (parameter addresses, geometry): the host builds it once instead of every step -- at the 12^3 / 6^3 levels a block's kernels take 60-70 us and
     its host code took 100 us (tools/host_profile.py), the queue ran dry there.  Parameters keep their addresses for the life of a module; a new
     key (another net, a moved parameter) simply adds an entry.  Returns (buffers, bns)."""
-    import ctypes
-    key = (w1.data_ptr(), w2.data_ptr(), 0 if ws is None else ws.data_ptr(), w1.shape[0], Ca, Cb, dtype, tiles_total, with_backward, dims, rs_variant_epoch())
+    key = (w1.data_ptr(), w2.data_ptr(), 0 if ws is None else ws.data_ptr(), w1.shape[0], Ca, Cb, dtype, tiles_total, with_backward, dims, mixed,
+           rs_variant_epoch())
     ent = _BLOCK_PACK_CACHE.get(key)
     if ent is None:
-        specs, bns = block_pack_specs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims)
-        dt = _DT[dtype]
-        n = len(specs)
-        sizes = [_L().rsuper_conv3_packed_elems(dt, sp[3], sp[4], _spec_cols(sp), sp[7]) for sp in specs]
-        offs = [0]
-        for z in sizes:
-            offs.append(offs[-1] + z)
-        desc = (ctypes.c_int * (6 * n))(*[v for sp in specs for v in (sp[0], sp[3], sp[4], sp[5], sp[6], sp[7])])
-        wa = (ctypes.c_void_p * n)(*[sp[1].data_ptr() for sp in specs])
-        wb = (ctypes.c_void_p * n)(*[(sp[2].data_ptr() if sp[2] is not None else None) for sp in specs])
-        oe = (ctypes.c_size_t * n)(*offs[:-1])
+        specs, bns = block_pack_specs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims, mixed)
         if len(_BLOCK_PACK_CACHE) > 1024:
             _BLOCK_PACK_CACHE.clear()
-        ent = _BLOCK_PACK_CACHE[key] = (dt, n, desc, wa, wb, oe, offs, bns)
-    dt, n, desc, wa, wb, oe, offs, bns = ent
-    buf = torch.empty((offs[-1],), device=w1.device, dtype=dtype)
-    _l.check(_L().rsuper_conv3_pack_weights_batch(dt, n, desc, wa, wb, oe, _ptr(buf), _stream()), 'pack_weights_batch')
-    return [buf[offs[i]:offs[i + 1]] for i in range(n)], bns
+        ent = _BLOCK_PACK_CACHE[key] = _pack_desc(dtype, specs) + (bns,)
+    return _pack_launch(ent[0], ent[1], dtype, w1.device), ent[2]
 
 
 def rs_variant_epoch():
-    """The igemm variant / tile-fill switches change pick_bn's answers: part of the cache key."""
-    return (_L().rsuper_conv3_variant(-1), os.environ.get('RSUPER_BN_FILL', '512'), os.environ.get('RSUPER_SPLIT_DGRAD', '1'))
+    """What pick_bn's answers and the split of the data gradient depend on besides the launch shape: part of the cache key.  (The library's other
+    dispatch switches are read once per process; the registered workspace is set once, before the first launch.)"""
+    return (_L().rsuper_conv3_variant(-1), os.environ.get('RSUPER_SPLIT_DGRAD', '1'))
 
 
-def block_pack_specs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims=None):
+def block_pack_specs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims=None, mixed=False):
     """The (up to) four fragment buffers a BasicBlock needs: forward conv1(+shortcut), forward conv2, data-gradient
-    conv2, data-gradient conv1(+shortcut).  Returns (specs, bns) in that order."""
+    conv2, data-gradient conv1(+shortcut).  Returns (specs, bns) in that order.  mixed: one of the block's two sources is normalised, the other raw
+    (only conv1's forward launch reads them; every data gradient reads raw dY sources)."""
     Cout, Cin = w1.shape[0], Ca + Cb
     has_sc = ws is not None
     nc1 = Cout * (2 if has_sc else 1)
-    bn1, bn2 = pick_bn(nc1, dtype, tiles_total, dims, epi=0), pick_bn(Cout, dtype, tiles_total, dims, epi=0)
+    bn1, bn2 = pick_bn(nc1, dtype, tiles_total, dims, epi=0, mixed=mixed), pick_bn(Cout, dtype, tiles_total, dims, epi=0)
     specs = [(0, w1, ws, Ca, Cb, Cout, Cout if has_sc else 0, bn1), (0, w2, None, Cout, 0, Cout, 0, bn2)]
     bns = [bn1, bn2]
     if with_backward:
@@ -263,7 +237,6 @@ class KernelTimer:
     def _event(self):
         if self.fenced:
             return torch.cuda.Event(enable_timing=True)
-        import ctypes
         h = ctypes.c_void_p()
         _l.check(_L().rsuper_timer_event_create(ctypes.byref(h)), 'timer_event_create')
         self._pool.append(h)
@@ -278,7 +251,6 @@ class KernelTimer:
     def _elapsed(self, a, b):
         if self.fenced:
             return a.elapsed_time(b)
-        import ctypes
         ms = ctypes.c_float()
         _l.check(_L().rsuper_timer_event_elapsed_ms(a, b, ctypes.byref(ms)), 'timer_event_elapsed')
         return float(ms.value)
@@ -460,17 +432,14 @@ def igemm(epi, a, b, packed, n_cols, bn, dims, out, out_ld=None, res=None, part=
     ra = (None, 0) if res is None else (_ptr(res.t, res.off), res.ld)
 
     def run():
+        args = (dt, epi, *a.args(), *(b.args() if b is not None else _NONE), _ptr(packed), n_cols, bn,
+                N, D, H, W, _ptr(out), out.shape[-1] if out_ld is None else out_ld, ra[0], ra[1], _ptr(part),
+                *(ea.args() if ea is not None else _NONE), *(eb.args() if eb is not None else _NONE))
         if out2 is not None:
             delta = (out2.data_ptr() - out.data_ptr()) // out.element_size()
-            _l.check(_L().rsuper_conv3_igemm_split_out(dt, epi, *a.args(), *(b.args() if b is not None else _NONE), _ptr(packed), n_cols, bn,
-                                                       N, D, H, W, _ptr(out), out.shape[-1] if out_ld is None else out_ld, ra[0], ra[1], _ptr(part),
-                                                       *(ea.args() if ea is not None else _NONE), *(eb.args() if eb is not None else _NONE),
-                                                       out_split, delta, _stream()), 'conv3_igemm_split_out')
-            return
-        _l.check(_L().rsuper_conv3_igemm(dt, epi, *a.args(), *(b.args() if b is not None else _NONE), _ptr(packed), n_cols, bn,
-                                         N, D, H, W, _ptr(out), out.shape[-1] if out_ld is None else out_ld, ra[0], ra[1], _ptr(part),
-                                         *(ea.args() if ea is not None else _NONE), *(eb.args() if eb is not None else _NONE),
-                                         _stream()), 'conv3_igemm')
+            _l.check(_L().rsuper_conv3_igemm_split_out(*args, out_split, delta, _stream()), 'conv3_igemm_split_out')
+        else:
+            _l.check(_L().rsuper_conv3_igemm(*args, _stream()), 'conv3_igemm')
     if TIMER is not None:
         K = a.C + (b.C if b is not None else 0)
         TIMER.launch('conv3d_igemm_fwd' if epi == 0 else 'conv3d_igemm_dgrad', 2.0 * N * D * H * W * n_cols * K * 27, run)
@@ -534,7 +503,6 @@ def flush_wgrad_reduces(stats=None):
     stats: up to two (part, cnt, mode, split) statistics buffers finalised by the SAME launch (rsuper_conv3_wgrad_reduce_batch_stats: the arithmetic of
     stats_finalize, bit-identical); returns the list of their results in stats_finalize's form.  Without deferred reductions to ride on they are finalised
     by their own launches."""
-    import ctypes
     if stats and (not _DEFERRED or not FUSE_STATS_REDUCE or len(stats) > 2 or len(_DEFERRED) > 48):
         res = [stats_finalize(p_, cnt, mode=mode, split=split) for p_, cnt, mode, split in stats]
         flush_wgrad_reduces()
@@ -694,20 +662,20 @@ class BasicBlockFn(torch.autograd.Function):
         cnt = D * H * W
         sa = Src(xa, mr=mra)
         sb = None if xb is None else Src(xb, mr=mrb)
+        mixed = xb is not None and (mra is None) != (mrb is None)      # conv1's launch: whatever width it was packed for, `part` and the kernel follow this
         # conv1 (+ shortcut): one GEMM
         nc1 = Cout * (2 if has_sc else 1)
         if packs is None:                  # one pack launch per block and direction (fragments stay hot in L2 for the convs below)
             # with gradients wanted, the data-gradient fragments are packed by the same launch (one pack launch per block instead of
             # two; they are read once, much later, so being cold in L2 by then costs nothing measurable)
-            both = os.environ.get('RSUPER_PACK_BOTH', '1') == '1' and any(ctx.needs_input_grad)
-            packs = block_packs(w1, w2, ws, Ca, Cb, dt, tiles * N, both, dims)
+            packs = block_packs(w1, w2, ws, Ca, Cb, dt, tiles * N, any(ctx.needs_input_grad), dims, mixed)
         bn1, wp1 = packs[1][0], packs[0][0]
-        part = part_buffer(dt, dims, nc1, bn1, dev)
+        part = part_buffer(dt, dims, nc1, bn1, dev, mixed=mixed)
         # [y1 | shortcut] halves narrower than a 128-byte line (32 bf16 channels: up4.0): two tensors instead of an interleaved one, so that conv2's staging,
         # its weight gradient, the mask of its data gradient and the InstanceNorm-backward tail read whole cache lines (rsuper_conv3_igemm_split_out; the
         # depth-reuse kernel's epilogue only -- other kernels keep the interleaved output)
         split_ys = (has_sc and Cout * xa.element_size() < 128 and Cout % 32 == 0 and os.environ.get('RSUPER_SPLIT_YS', '1') == '1'
-                    and _L().rsuper_conv3_kd_bn(_DT[dt], 0, N, D, H, W, nc1, 0) == bn1)
+                    and igemm_plan(dt, 0, dims, nc1, bn1, mixed)[0] == _l.IGEMM_KD)
         if split_ys:
             ys2 = torch.empty((2, N, D, H, W, Cout), device=dev, dtype=dt)
             ys, sc_t = ys2[0], ys2[1]
@@ -759,7 +727,7 @@ class BasicBlockFn(torch.autograd.Function):
             mr_y1 = stats_finalize(part1, OD * OH * OW, split=Cout)[0]
         dims2 = (N, OD, OH, OW)
         tiles2 = _L().rsuper_conv3_tiles(OD, OH, OW)
-        bn2 = pick_bn(Cout, dt, tiles2 * N, dims2)
+        bn2 = pick_bn(Cout, dt, tiles2 * N, dims2, epi=0)
         wp2 = pack_weights(dt, 0, w2, None, Cout, 0, Cout, 0, bn2)
         out = torch.empty((N, OD, OH, OW, Cout), device=dev, dtype=dt)
         part2 = part_buffer(dt, dims2, Cout, bn2, dev)
@@ -785,7 +753,7 @@ class BasicBlockFn(torch.autograd.Function):
         sdo = Src(dout)
         # conv2 at the half resolution: as in the stride-1 block
         tiles2 = _L().rsuper_conv3_tiles(OD, OH, OW)
-        bn = pick_bn(Cout, dt, tiles2 * N, dims2)
+        bn = pick_bn(Cout, dt, tiles2 * N, dims2, epi=1)
         wpd2 = pack_weights(dt, 1, w2, None, Cout, 0, Cout, 0, bn)
         g1 = torch.empty((N, OD, OH, OW, Cout), device=dev, dtype=dt)
         part = part_buffer(dt, dims2, Cout, bn, dev, epi=1)
@@ -806,7 +774,7 @@ class BasicBlockFn(torch.autograd.Function):
             subsample2_scatter(dy1, dfull, 0, dims)
             subsample2_scatter(dout, dfull, Cout, dims)
         if not k_dgrad:
-            bnd = pick_bn(Ca, dt, tiles * N, dims)
+            bnd = pick_bn(Ca, dt, tiles * N, dims, epi=1)
             wpd1 = pack_weights(dt, 1, w1, ws, Cout, Cout, Ca, 0, bnd)
             part0 = part_buffer(dt, dims, Ca, bnd, dev, epi=1)
             igemm(1, Src(dfull, C=Cout), Src(dfull, C=Cout, off=Cout), wpd1, Ca, bnd, dims, g0, part=part0, ea=sa)
@@ -1108,7 +1076,7 @@ class Conv3Fn(torch.autograd.Function):
         assert tuple(w.shape[1:]) == (Cin, 3, 3, 3) and Cout % 8 == 0 and w.dtype == torch.float32
         dt, dims = x.dtype, (N, D, H, W)
         tiles = _L().rsuper_conv3_tiles(D, H, W) * N
-        bn = pick_bn(Cout, dt, tiles, dims)
+        bn = pick_bn(Cout, dt, tiles, dims, epi=0)
         wc = w.contiguous()
         out = torch.empty((N, D, H, W, Cout), device=x.device, dtype=dt)
         igemm(0, Src(x), None, pack_weights(dt, 0, wc, None, Cin, 0, Cout, 0, bn), Cout, bn, dims, out)
@@ -1124,7 +1092,7 @@ class Conv3Fn(torch.autograd.Function):
         dout = dout.contiguous()
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            bn = pick_bn(Cin, dt, _L().rsuper_conv3_tiles(D, H, W) * N, dims)
+            bn = pick_bn(Cin, dt, _L().rsuper_conv3_tiles(D, H, W) * N, dims, epi=0)      # raw dY, no mask: the forward epilogue on flipped taps
             dx = torch.empty_like(x)
             igemm(0, Src(dout), None, pack_weights(dt, 1, w, None, Cout, 0, Cin, 0, bn), Cin, bn, dims, dx)
         if ctx.needs_input_grad[1]:

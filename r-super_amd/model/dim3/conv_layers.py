@@ -45,25 +45,25 @@ class BasicBlock(nn.Module):
         w1, w2, ws = self.weights()
         packs = getattr(self, '_packs', None)        # set by UNet.forward (whole-network batched weight packing)
         if packs is None and not torch.is_grad_enabled():
-            packs = self._cached_forward_packs(xa, xb, w1, w2, ws)
+            packs = self._cached_forward_packs(xa, xb, w1, w2, ws, xb is not None and (mra is None) != (mrb is None))
         if self.stride == 2:
             assert xb is None
             return ops.BasicBlockFn.apply(xa, mra, None, None, w1, w2, ws, None, 2)
         return ops.BasicBlockFn.apply(xa, mra, xb, mrb, w1, w2, ws, packs, 1)
 
-    def _cached_forward_packs(self, xa, xb, w1, w2, ws):
+    def _cached_forward_packs(self, xa, xb, w1, w2, ws, mixed):
         """Inference (no_grad): the MFMA fragment buffers only change when the weights do, so sliding-window inference packs
         each layer once instead of once per window.  Keyed on the parameters' version counters, ops.WEIGHTS_EPOCH (the fused optimiser
         writes parameters through raw pointers) and the launch geometry."""
         N, D, H, W, Ca = xa.shape
         Cb = 0 if xb is None else xb.shape[-1]
         tiles_total = ops._L().rsuper_conv3_tiles(D, H, W) * N
-        key = (ops.WEIGHTS_EPOCH, w1._version, w2._version, None if ws is None else ws._version, w1.data_ptr(), xa.dtype, Ca, Cb, tiles_total)
+        key = (ops.WEIGHTS_EPOCH, w1._version, w2._version, None if ws is None else ws._version, w1.data_ptr(), xa.dtype, Ca, Cb, tiles_total, mixed)
         hit = getattr(self, '_pack_cache', None)
         # ... and on the identity of the parameters: a replaced parameter can inherit address and version counter of the one it replaced
         if hit is not None and hit[0] == key and all(r() is w for r, w in zip(hit[2], (w1, w2, ws)) if w is not None):
             return hit[1]
-        specs, bns = ops.block_pack_specs(w1, w2, ws, Ca, Cb, xa.dtype, tiles_total, False, (N, D, H, W))
+        specs, bns = ops.block_pack_specs(w1, w2, ws, Ca, Cb, xa.dtype, tiles_total, False, (N, D, H, W), mixed)
         packs = (ops.pack_weights_batch(xa.dtype, specs), bns)
         self._pack_cache = (key, packs, tuple(weakref.ref(w) if w is not None else None for w in (w1, w2, ws)))
         return packs

@@ -150,7 +150,25 @@ def check_conv_mixed_sources(N, S, Ca, Cb, Cout, seed=0):
     e1 = relerr(from_cl(out), ref)
     mr_ref = stats_ref(rnd(ref, 'bf16'))
     e2 = relerr(mr.cpu()[..., 0], mr_ref[..., 0]) + relerr(mr.cpu()[..., 1], mr_ref[..., 1])
-    return result(f'conv_mixed_sources[bf16 N{N} S{S} {Ca}n+{Cb}raw->{Cout}]', max(e1, e2), TOL['bf16'], f'out {e1:.2e} stats {e2:.2e} bn {bn}')
+    # ... and the same GEMM as [conv1 | shortcut] of a BasicBlock (2 x Cout / 2 columns) through BasicBlockFn, which asks the plan with the block's own `mixed`
+    # bit: widths, the rows of its torch.empty `part` buffers and the split-output probe must all follow the ordinary kernel (before, the probe
+    # and block_pack_specs asked without the bit and the launch was refused).  Same reference arithmetic, same tolerance, and nothing unwritten is read.
+    Cq = Cout // 2
+    assert ops.igemm_plan(dt, 0, dims, 2 * Cq, mixed=False)[0] == _lib.IGEMM_KD and ops.igemm_plan(dt, 0, dims, 2 * Cq, mixed=True)[0] != _lib.IGEMM_KD
+    w2 = _rng_t(seed + 8, (Cq, Cq, 3, 3, 3), 1.0 / math.sqrt(27 * Cq))
+    wsc = _rng_t(seed + 9, (Cq, Ca + Cb, 3, 3, 3), 1.0 / math.sqrt(27 * (Ca + Cb)))
+    with torch.no_grad():
+        yb, mr_yb = ops.BasicBlockFn.apply(to_cl(xa, dt), stats_ref(xa).to(DEV), to_cl(xb, dt), None, w1[:Cq].contiguous().to(DEV), w2.to(DEV), wsc.to(DEV), None, 1)
+    torch.cuda.synchronize()
+    y1 = rnd(F.conv3d(xh, rnd(w1[:Cq], 'bf16'), padding=1), 'bf16')
+    sc = rnd(F.conv3d(xh, rnd(wsc, 'bf16'), padding=1), 'bf16')
+    ref_b = F.conv3d(F.relu(uo.instance_norm(y1)).bfloat16().float(), rnd(w2, 'bf16'), padding=1) + sc
+    e3 = relerr(from_cl(yb), ref_b)
+    mr_refb = stats_ref(rnd(ref_b, 'bf16'))
+    e4 = relerr(mr_yb.cpu()[..., 0], mr_refb[..., 0]) + relerr(mr_yb.cpu()[..., 1], mr_refb[..., 1])
+    finite = bool(torch.isfinite(yb.float()).all()) and bool(torch.isfinite(mr_yb).all())
+    return result(f'conv_mixed_sources[bf16 N{N} S{S} {Ca}n+{Cb}raw->{Cout}]', max(e1, e2, e3, e4) if finite else float('nan'), TOL['bf16'],
+                  f'out {e1:.2e} stats {e2:.2e} bn {bn} block out {e3:.2e} stats {e4:.2e}')
 
 
 def _block_ref(mode, xa, xb, w1, ws, dy1, dys):
