@@ -232,6 +232,10 @@ int rsuper_pointwise_wgrad(int dtype, const float* dy, int ldy, const float* x, 
  * split > 0 writes two contiguous tables instead, [N][split][2] followed by [N][C-split][2] (the column groups of a fused
  * conv1 + shortcut GEMM, or the two sources of a concatenated input), so each can be handed to a kernel as-is. */
 int rsuper_stats_finalize(const float* part, int N, int nblk, int C, double cnt, float eps, int mode, int split, float* out, void* stream);
+/* The bandwidth-bound kernels around the convolutions (InstanceNorm backward tail, max pool, subsample, trilinear forward, plane partial sums):
+ * 1 (default) = the tuned kernels and grids, 0 = the ones they replaced -- results are bit-identical, the switch serves A/B runs and tests
+ * (RSUPER_GLUE_KERNELS=0 in the environment selects 0 at start-up).  Any other v queries.  Returns the value in effect. */
+int rsuper_glue_variant(int v);
 /* dx = rstd * (g - gm0 - x_n * gm1) [+ add1] [+ add2] */
 int rsuper_in_bwd_finalize(int dtype, const void* g, int ldg, const void* x, int ldx, const float* mr, const float* gm,
                            const void* add1, int lda1, const void* add2, int lda2, void* out, int ldo,

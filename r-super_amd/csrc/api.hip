@@ -393,6 +393,8 @@ int rsuper_stats_finalize(const float* part, int N, int nblk, int C, double cnt,
     return rs_launch_stats_finalize(part, N, nblk, C, cnt, eps, mode, split, out, ST(stream));
 }
 
+int rsuper_glue_variant(int v) { return rs_glue_variant(v); }
+
 int rsuper_in_bwd_finalize(int dtype, const void* g, int ldg, const void* x, int ldx, const float* mr, const float* gm,
                            const void* add1, int lda1, const void* add2, int lda2, void* out, int ldo,
                            int N, int vox, int C, void* stream) {

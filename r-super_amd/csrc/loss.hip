@@ -29,6 +29,9 @@ __device__ __forceinline__ float sigmoidf(float x) { float s, b; sig_bce(x, 0.f,
 
 // grid: (blocks, planes).  p.pblk (calculate_loss, round 6): every block stores its six sums to pblk[plane][block][6], plane_sums_reduce_kernel adds them in block
 // order; p.sums (the one-launch form of rsuper_plane_partials_fwd / _fwd2): [planes][6] doubles, pre-zeroed, accumulated with f64 atomics.
+// PIPE: the wide path requests the operands of its next trip before it evaluates the current one (the exp / log / rcp chain of 16 voxels covers the
+// round trip; the plain loop waited for every trip on its own).  Each thread adds the same voxels in the same order: the sums are bit-identical.
+template <bool PIPE>
 __global__ __launch_bounds__(256) void plane_partials_fwd_kernel(PlaneParams p) {
     const int plane = blockIdx.y;
     const size_t base = (size_t)plane * p.V;
@@ -59,20 +62,39 @@ __global__ __launch_bounds__(256) void plane_partials_fwd_kernel(PlaneParams p) 
             b *= kk;
             s[0] += b; s[1] += sg * kk; s[2] += sg * tt * kk; s[3] += tt * kk; s[5] += b * (w2b ? 0.f : 1.f);
         };
-        for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16; i < (size_t)p.V; i += (size_t)gridDim.x * 256 * 16) {
-            float4 q[4];
+        struct Trip { float4 q[4]; uint4 tq, kq, wq; };
+        auto fetch = [&](size_t i) {
+            Trip r;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) q[u] = *(const float4*)(x + i + 4 * u);
-            const uint4 tq = t ? *(const uint4*)(t + i) : make_uint4(0, 0, 0, 0);
-            const uint4 kq = k ? *(const uint4*)(k + i) : make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
-            const uint4 wq = w2 ? *(const uint4*)(w2 + i) : make_uint4(0, 0, 0, 0);
-            const uint32_t tw[4] = {tq.x, tq.y, tq.z, tq.w}, kw[4] = {kq.x, kq.y, kq.z, kq.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w};
+            for (int u = 0; u < 4; ++u) r.q[u] = *(const float4*)(x + i + 4 * u);
+            r.tq = t ? *(const uint4*)(t + i) : make_uint4(0, 0, 0, 0);
+            r.kq = k ? *(const uint4*)(k + i) : make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
+            r.wq = w2 ? *(const uint4*)(w2 + i) : make_uint4(0, 0, 0, 0);
+            return r;
+        };
+        auto eval = [&](const Trip& r) {
+            const uint32_t tw[4] = {r.tq.x, r.tq.y, r.tq.z, r.tq.w}, kw[4] = {r.kq.x, r.kq.y, r.kq.z, r.kq.w}, ww[4] = {r.wq.x, r.wq.y, r.wq.z, r.wq.w};
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const float xv[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+                const float xv[4] = {r.q[u].x, r.q[u].y, r.q[u].z, r.q[u].w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) term(xv[j], (tw[u] >> (8 * j)) & 0xFFu, (kw[u] >> (8 * j)) & 0xFFu, (ww[u] >> (8 * j)) & 0xFFu);
             }
+        };
+        const size_t step = (size_t)gridDim.x * 256 * 16;
+        size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
+        if (PIPE) {
+            if (i < (size_t)p.V) {
+                Trip cur = fetch(i);
+                for (i += step; i < (size_t)p.V; i += step) {
+                    const Trip nxt = fetch(i);
+                    eval(cur);
+                    cur = nxt;
+                }
+                eval(cur);
+            }
+        } else {
+            for (; i < (size_t)p.V; i += step) eval(fetch(i));
         }
         i0 = (size_t)p.V;                                          // nothing left for the narrow loop
     }
@@ -371,7 +393,8 @@ int rs_launch_plane_sums_reduce(const double* pblk, int rows, int nb, float* out
 int rs_launch_plane_partials(const PlaneParams& p, int planes, int bwd, hipStream_t st) {
     const int blocks = rs_plane_partials_blocks(p.V);
     if (!bwd) {
-        hipLaunchKernelGGL(plane_partials_fwd_kernel, dim3(blocks, planes), dim3(256), 0, st, p);
+        if (rs_glue_variant(-1)) hipLaunchKernelGGL(plane_partials_fwd_kernel<true>, dim3(blocks, planes), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(plane_partials_fwd_kernel<false>, dim3(blocks, planes), dim3(256), 0, st, p);
     } else {
         int b2 = (int)((p.V + 1023) / 1024);
         if (b2 > 256) b2 = 256;

@@ -71,6 +71,7 @@ int rs_launch_depthwise(const float* x, const float* w, float* y, int N, int D, 
 int rs_launch_depthwise_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int D, int H, int W, int C, hipStream_t st);
 int rs_launch_stats_finalize(const float* part, int N, int nblk, int C, double cnt, float eps, int mode, int split, float* out, hipStream_t st);
 int rs_elem_blocks(size_t items);
+int rs_glue_variant(int v);      // 1: tuned bandwidth-bound kernels (default), 0: the ones they replaced; other values query
 int rs_launch_in_bwd(const InBwdParams& p, int dtype, hipStream_t st);
 int rs_launch_pool(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st);
 int rs_launch_subsample(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st);

@@ -142,6 +142,70 @@ __global__ __launch_bounds__(256) void in_bwd_finalize_kernel(InBwdParams p) {
     }
 }
 
+// Mid-sized tensors (48^3 and 24^3 of the UNet step): the kernel above runs one 16-byte vector per thread there, so a wave spends its life on its
+// 4 x KP constants and one round trip (3.0-4.7 TB/s against 5.5 at 96^3).  Here a thread owns U vectors 256 apart (same channel slot: CV is a power
+// of two dividing 256), requests all their operands before the first use and loads its constants once; a quarter / half of the blocks.  The
+// arithmetic per element is the kernel's above, so the output is bit-identical.
+template <typename T, int U>
+__global__ __launch_bounds__(256) void in_bwd_finalize2_kernel(InBwdParams p, int cv_shift) {
+    constexpr int KP = Elem<T>::KP;
+    const uint32_t CV = 1u << cv_shift;
+    const uint32_t total = (uint32_t)p.vox * CV;                 // per sample (< 2^32: checked by the launcher)
+    const uint32_t n = blockIdx.y;
+    const uint32_t i0 = blockIdx.x * (256u * U) + threadIdx.x;
+    if (i0 >= total) return;
+    const T* gp = (const T*)p.g + (size_t)n * p.vox * p.ldg;
+    const T* xp = (const T*)p.x + (size_t)n * p.vox * p.ldx;
+    const T* a1p = p.add1 ? (const T*)p.add1 + (size_t)n * p.vox * p.lda1 : nullptr;
+    const T* a2p = p.add2 ? (const T*)p.add2 + (size_t)n * p.vox * p.lda2 : nullptr;
+    T* op = (T*)p.out + (size_t)n * p.vox * p.ldo;
+    const uint32_t c = (i0 & (CV - 1u)) * KP;
+    uint4 gq[U], xq[U], a1q[U], a2q[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t i = i0 + 256u * u;
+        const uint32_t v = (i < total ? i : i0) >> cv_shift;     // a vector past the end re-reads the first one and is not stored
+        gq[u] = *(const uint4*)(gp + (size_t)v * p.ldg + c);
+        xq[u] = *(const uint4*)(xp + (size_t)v * p.ldx + c);
+        a1q[u] = make_uint4(0, 0, 0, 0); a2q[u] = make_uint4(0, 0, 0, 0);
+        if (a1p) a1q[u] = *(const uint4*)(a1p + (size_t)v * p.lda1 + c);
+        if (a2p) a2q[u] = *(const uint4*)(a2p + (size_t)v * p.lda2 + c);
+    }
+    float mu[KP], rs[KP], m1[KP], m2[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const size_t o = ((size_t)n * p.C + c + j) * 2;
+        mu[j] = p.mr[o]; rs[j] = p.mr[o + 1]; m1[j] = p.gm[o]; m2[j] = p.gm[o + 1];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t i = i0 + 256u * u;
+        if (i >= total) break;
+        const uint32_t v = i >> cv_shift;
+        float g[KP], x[KP], o[KP];
+        unpack16<T>(gq[u], g);
+        unpack16<T>(xq[u], x);
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const float xn = (x[j] - mu[j]) * rs[j];
+            o[j] = rs[j] * (g[j] - m1[j] - xn * m2[j]);
+        }
+        if (a1p) {
+            float a[KP];
+            unpack16<T>(a1q[u], a);
+#pragma unroll
+            for (int j = 0; j < KP; ++j) o[j] += a[j];
+        }
+        if (a2p) {
+            float a[KP];
+            unpack16<T>(a2q[u], a);
+#pragma unroll
+            for (int j = 0; j < KP; ++j) o[j] += a[j];
+        }
+        *(uint4*)(op + (size_t)v * p.ldo + c) = pack16<T>(o);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ max pool 2x2x2
 // grid: (blocks over output voxels of one sample, N).  Output partial stats for the next InstanceNorm.
 template <typename T>
@@ -177,6 +241,62 @@ __global__ void maxpool_fwd_kernel(PoolParams p) {
             for (int j = 0; j < KP; ++j) { s1[j] += m[j]; s2[j] += m[j] * m[j]; }
         }
     if (p.part) block_channel_sums<KP>(s1, s2, p.C, CV, VL, vl, s, active, p.part + ((size_t)n * gridDim.x + blockIdx.x) * p.C * 2);
+}
+
+// Small volumes (24^3 and below): the grid above is the row count of `part` (3 blocks per sample for a 6^3 output), and a thread walks its voxels one
+// round trip after the other.  Here gridDim.z blocks share a row: block z owns CV / gridDim.z of the channel vectors with the same VL voxel lanes, so
+// every thread keeps the voxel walk and block_channel_sums the lane order of the kernel above -- y and the rows of `part` are bit-identical -- and the
+// 8 x U input vectors of U voxels are requested before the first is used.
+template <typename T, int U>
+__global__ __launch_bounds__(256) void maxpool_fwd2_kernel(PoolParams p) {
+    constexpr int KP = Elem<T>::KP;
+    const int CV = p.C / KP, VL = 256 / CV;
+    const int CVb = CV / gridDim.z;                              // channel vectors of this block (blockDim.x = CVb * VL)
+    const int vl = threadIdx.x / CVb, s = blockIdx.z * CVb + threadIdx.x % CVb;
+    const bool active = vl < VL;
+    const int n = blockIdx.y;
+    const int OD = p.D / 2, OH = p.H / 2, OW = p.W / 2;
+    const int ovox = OD * OH * OW;
+    const int per_blk = (ovox + gridDim.x - 1) / gridDim.x;
+    const int v0 = blockIdx.x * per_blk, v1 = min(ovox, v0 + per_blk);
+    float s1[KP], s2[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    if (active)
+        for (int v = v0 + vl; v < v1; v += U * VL) {
+            uint4 q[U][8];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int vv = v + u * VL < v1 ? v + u * VL : v;
+                const int ow = vv % OW, oh = (vv / OW) % OH, od = vv / (OW * OH);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int d = od * 2 + (k >> 2), h = oh * 2 + ((k >> 1) & 1), w = ow * 2 + (k & 1);
+                    q[u][k] = *(const uint4*)((const T*)p.x + ((((size_t)n * p.D + d) * p.H + h) * p.W + w) * (size_t)p.ldx + s * KP);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (v + u * VL >= v1) break;
+                float m[KP];
+#pragma unroll
+                for (int j = 0; j < KP; ++j) m[j] = -INFINITY;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    float x[KP];
+                    unpack16<T>(q[u][k], x);
+#pragma unroll
+                    for (int j = 0; j < KP; ++j) m[j] = fmaxf(m[j], x[j]);
+                }
+                *(uint4*)((T*)p.y + ((size_t)n * ovox + v + u * VL) * p.ldy + s * KP) = pack16<T>(m);
+#pragma unroll
+                for (int j = 0; j < KP; ++j) { s1[j] += m[j]; s2[j] = fmaf(m[j], m[j], s2[j]); }      // the fused form maxpool_fwd_kernel compiles to (it matters in f32)
+            }
+        }
+    const int Cb = CVb * KP;
+    if (p.part)
+        block_channel_sums<KP>(s1, s2, Cb, CVb, VL, vl, threadIdx.x % CVb, active,
+                               p.part + (((size_t)n * gridDim.x + blockIdx.x) * p.C + (size_t)blockIdx.z * Cb) * 2);
 }
 
 // dx = dy routed to the FIRST maximum in (d,h,w) scan order (ATen max_pool3d keeps the first `>`), else 0.
@@ -233,7 +353,8 @@ template <typename T>
 __global__ void subsample_fwd_kernel(PoolParams p) {
     constexpr int KP = Elem<T>::KP;
     const int CV = p.C / KP, VL = 256 / CV;
-    const int vl = threadIdx.x / CV, s = threadIdx.x % CV;
+    const int CVb = CV / gridDim.z;                              // gridDim.z blocks share a row of `part` (small volumes, see maxpool_fwd2_kernel)
+    const int vl = threadIdx.x / CVb, s = blockIdx.z * CVb + threadIdx.x % CVb;
     const bool active = vl < VL;
     const int n = blockIdx.y;
     const int OD = (p.D + 1) / 2, OH = (p.H + 1) / 2, OW = (p.W + 1) / 2;
@@ -253,7 +374,10 @@ __global__ void subsample_fwd_kernel(PoolParams p) {
 #pragma unroll
             for (int j = 0; j < KP; ++j) { s1[j] += m[j]; s2[j] += m[j] * m[j]; }
         }
-    if (p.part) block_channel_sums<KP>(s1, s2, p.C, CV, VL, vl, s, active, p.part + ((size_t)n * gridDim.x + blockIdx.x) * p.C * 2);
+    const int Cb = CVb * KP;
+    if (p.part)
+        block_channel_sums<KP>(s1, s2, Cb, CVb, VL, vl, threadIdx.x % CVb, active,
+                               p.part + (((size_t)n * gridDim.x + blockIdx.x) * p.C + (size_t)blockIdx.z * Cb) * 2);
 }
 
 // dx[d, h, w] = dy[d / 2, h / 2, w / 2] at the even voxels, 0 elsewhere (every input voxel is written)
@@ -500,6 +624,109 @@ __global__ __launch_bounds__(256) void upsample_fwd2_kernel(UpParams p) {
         }
     }
     if (p.part) block_channel_sums<KP>(s1, s2, p.C, CV, VL, vl, s, active, p.part + ((size_t)n * gridDim.x + blockIdx.x) * p.C * 2);
+}
+
+// Third-generation forward.  upsample_fwd2 issues about 230 vector instructions per output vector, 14 of them quarter-rate 32-bit multiplies: 1090
+// issue cycles per wave and output, which alone is 98 us at 96^3 x 64 channels -- what it measures.  The source indices and weights of an output
+// coordinate depend on that coordinate alone, so each block builds them once per axis in LDS: entry = byte offsets of the two source indices times the
+// axis' stride, and the weights (1 - l, l) -- lin_coord's values.  Per output: three 16-byte LDS reads, 14 32-bit adds for the eight corner offsets,
+// the same weight products ((d * h) * w) and the same accumulation (k = 0..7, fused multiply-add on f32 pairs) as upsample_fwd2: about 175
+// instructions, none of them quarter-rate.  A thread keeps upsample_fwd2's voxel walk, and gridDim.z blocks may share a row of `part` (see
+// maxpool_fwd2_kernel): y and `part` are bit-identical.  Measured 99.6 -> 92 us at 96^3 x 64 (profiles/glue_kernels_ab.md): issue was not the only
+// bound.  A second register set that keeps the next output's eight loads in flight during the accumulation measured the same (93 us) and was not
+// kept; what remains is 8 KB of L1 requests per KB written, which only sharing corners between neighbouring outputs (another voxel walk) removes.
+struct UpTab { uint32_t o0, o1; float l0, l1; };
+template <typename T>
+__global__ __launch_bounds__(256) void upsample_fwd3_kernel(UpParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int KP = Elem<T>::KP;
+    const int CV = p.C / KP, VL = 256 / CV;
+    const int CVb = CV / gridDim.z;                              // channel vectors of this block (blockDim.x = CVb * VL)
+    const int Cb = CVb * KP;
+    const int vl = threadIdx.x / CVb, s = blockIdx.z * CVb + threadIdx.x % CVb;
+    const bool active = vl < VL;
+    const int n = blockIdx.y;
+    const int ovox = p.OD * p.OH * p.OW;
+    const int per_blk = (ovox + gridDim.x - 1) / gridDim.x;
+    const int v0 = blockIdx.x * per_blk, v1 = min(ovox, v0 + per_blk);
+    const float sd = p.OD > 1 ? (float)(p.ID - 1) / (float)(p.OD - 1) : 0.f;
+    const float sh = p.OH > 1 ? (float)(p.IH - 1) / (float)(p.OH - 1) : 0.f;
+    const float sw = p.OW > 1 ? (float)(p.IW - 1) / (float)(p.OW - 1) : 0.f;
+    UpTab* tab = (UpTab*)(smem + (size_t)VL * Cb * 2 * sizeof(float));      // [OD] [OH] [OW], behind block_channel_sums' buffer
+    for (int t = threadIdx.x; t < p.OD + p.OH + p.OW; t += blockDim.x) {
+        const int axis = t < p.OD ? 0 : (t < p.OD + p.OH ? 1 : 2);
+        const int o = axis == 0 ? t : (axis == 1 ? t - p.OD : t - p.OD - p.OH);
+        const float sc = axis == 0 ? sd : (axis == 1 ? sh : sw);
+        const int I = axis == 0 ? p.ID : (axis == 1 ? p.IH : p.IW);
+        const uint32_t stride = (uint32_t)sizeof(T) * (uint32_t)p.ldx * (axis == 0 ? (uint32_t)(p.IH * p.IW) : (axis == 1 ? (uint32_t)p.IW : 1u));
+        int i0, i1; float l;
+        lin_coord(o, sc, I, i0, i1, l);
+        UpTab e;
+        e.o0 = (uint32_t)i0 * stride; e.o1 = (uint32_t)i1 * stride; e.l0 = 1.f - l; e.l1 = l;
+        tab[t] = e;
+    }
+    __syncthreads();
+    const UpTab* td = tab; const UpTab* th = tab + p.OD; const UpTab* tw = tab + p.OD + p.OH;
+    float s1[KP], s2[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    const char* xin = (const char*)((const T*)p.x + (size_t)n * p.ID * p.IH * p.IW * p.ldx + s * KP);
+    if (active && v0 + vl < v1) {
+        int v = v0 + vl;
+        int ow = v % p.OW, oh = (v / p.OW) % p.OH, od = v / (p.OW * p.OH);
+        T* yp = (T*)p.y + ((size_t)n * ovox + v) * p.ldy + s * KP;
+        const size_t ystep = (size_t)VL * p.ldy;
+        for (; v < v1; v += VL, yp += ystep) {
+            const UpTab ed = td[od], eh = th[oh], ew = tw[ow];
+            const uint32_t rows[4] = {ed.o0 + eh.o0, ed.o0 + eh.o1, ed.o1 + eh.o0, ed.o1 + eh.o1};
+            const float wdh[4] = {ed.l0 * eh.l0, ed.l0 * eh.l1, ed.l1 * eh.l0, ed.l1 * eh.l1};
+            uint4 q[8];
+            float wt[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                q[k] = *(const uint4*)(xin + (rows[k >> 1] + ((k & 1) ? ew.o1 : ew.o0)));
+                wt[k] = wdh[k >> 1] * ((k & 1) ? ew.l1 : ew.l0);
+            }
+            float acc[KP];
+            if (sizeof(T) == 2) {
+                f32x2_t a2[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a2[j] = f32x2_t{0.f, 0.f};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const uint32_t wq[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+                    const f32x2_t w2 = {wt[k], wt[k]};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const f32x2_t x2 = {__uint_as_float(wq[j] << 16), __uint_as_float(wq[j] & 0xffff0000u)};
+                        a2[j] = __builtin_elementwise_fma(w2, x2, a2[j]);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { acc[2 * j] = a2[j][0]; acc[2 * j + 1] = a2[j][1]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < KP; ++j) acc[j] = 0.f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    float x[KP];
+                    unpack16<T>(q[k], x);
+#pragma unroll
+                    for (int j = 0; j < KP; ++j) acc[j] = fmaf(wt[k], x[j], acc[j]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < KP; ++j) acc[j] = Elem<T>::rnd(acc[j]);
+            *(uint4*)yp = pack16<T>(acc);
+#pragma unroll
+            for (int j = 0; j < KP; ++j) { s1[j] += acc[j]; s2[j] = fmaf(acc[j], acc[j], s2[j]); }      // the fused form upsample_fwd2_kernel compiles to (it matters in f32)
+            ow += VL;
+            while (ow >= p.OW) { ow -= p.OW; if (++oh == p.OH) { oh = 0; ++od; } }
+        }
+    }
+    if (p.part)
+        block_channel_sums<KP>(s1, s2, Cb, CVb, VL, vl, threadIdx.x % CVb, active,
+                               p.part + (((size_t)n * gridDim.x + blockIdx.x) * p.C + (size_t)blockIdx.z * Cb) * 2);
 }
 
 // Backward: per-axis tables in LDS (for every input index: first contributing output, count <= 6, weights -- exactly
@@ -1217,10 +1444,47 @@ int rs_elem_blocks(size_t items) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
+// 1 (default): the tuned bandwidth-bound kernels of this file and of loss.hip (in_bwd_finalize2, maxpool_fwd2, upsample_fwd3, channel-split grids,
+// pipelined plane_partials_fwd); 0: the kernels and grids they replaced (A/B runs and tests/test_gpu_glue_kernels.py: results are bit-identical).
+// RSUPER_GLUE_KERNELS=0 in the environment selects 0 at start-up.
+int rs_glue_variant(int v) {
+    static int g = !(getenv("RSUPER_GLUE_KERNELS") && atoi(getenv("RSUPER_GLUE_KERNELS")) == 0);
+    if (v == 0 || v == 1) g = v;
+    return g;
+}
+
+// Channel split of the kernels that write statistics rows (max pool, subsample, trilinear forward): `rows` is the row count of `part` and their
+// gridDim.x.  Where rows * N leaves most of the chip idle, z blocks of CV / z channel vectors (at least 128 bytes of a voxel, at least one wave)
+// share a row.
+static int stat_csplit(int rows, int N, int CV) {
+    if (!rs_glue_variant(-1)) return 1;
+    const int VL = 256 / CV;
+    int z = 1;
+    while ((size_t)rows * N * z < 1024 && CV % (2 * z) == 0 && CV / (2 * z) >= 8 && (CV / (2 * z)) * VL >= 64) z *= 2;
+    return z;
+}
+
 int rs_launch_in_bwd(const InBwdParams& p, int dtype, hipStream_t st) {
     const int KP = dtype == RS_F32 ? 4 : 8;
     if ((size_t)p.vox * (p.C / KP) >= 0xFFFFFFFFull) return RS_ERR_UNSUPPORTED;
     const int blocks = rs_elem_blocks((size_t)p.vox * (p.C / KP));
+    // one or two vectors per thread on the grid below (up to 48^3 x 128 channels at bf16): several vectors per thread, all loads up front.  Larger
+    // tensors loop on 4096 blocks and run at the HBM rate already
+    const uint32_t CV = (uint32_t)(p.C / KP);
+    const size_t nb1 = ((size_t)p.vox * CV + 255) / 256;
+    if (rs_glue_variant(-1) && CV > 0 && (CV & (CV - 1)) == 0 && CV <= 256 && nb1 >= 256 && nb1 <= 8192) {
+        const int sh = __builtin_ctz(CV);
+        if (nb1 >= 1024) {
+            const dim3 grid((unsigned)((nb1 + 3) / 4), p.N);
+            if (dtype == RS_F32) hipLaunchKernelGGL((in_bwd_finalize2_kernel<float, 4>), grid, dim3(256), 0, st, p, sh);
+            else hipLaunchKernelGGL((in_bwd_finalize2_kernel<bf16_t, 4>), grid, dim3(256), 0, st, p, sh);
+        } else {
+            const dim3 grid((unsigned)((nb1 + 1) / 2), p.N);
+            if (dtype == RS_F32) hipLaunchKernelGGL((in_bwd_finalize2_kernel<float, 2>), grid, dim3(256), 0, st, p, sh);
+            else hipLaunchKernelGGL((in_bwd_finalize2_kernel<bf16_t, 2>), grid, dim3(256), 0, st, p, sh);
+        }
+        return rs_check_launch();
+    }
     if (dtype == RS_F32) hipLaunchKernelGGL(in_bwd_finalize_kernel<float>, dim3(blocks, p.N), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(in_bwd_finalize_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), 0, st, p);
     return rs_check_launch();
@@ -1232,12 +1496,21 @@ int rs_launch_pool(const PoolParams& p, int dtype, int bwd, int blocks, hipStrea
     if (CV > 256) return RS_ERR_UNSUPPORTED;
     if (!bwd) {
         const size_t smem = (size_t)(256 / CV) * p.C * 2 * sizeof(float);
-        if (dtype == RS_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
-        else hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);
+        if (rs_glue_variant(-1) && (size_t)blocks * p.N < 1024) {                  // small volumes: channel-split grid, four voxels of loads in flight
+            const int z = stat_csplit(blocks, p.N, CV);
+            const dim3 grid(blocks, p.N, z), blk(z == 1 ? 256 : (CV / z) * (256 / CV));
+            if (dtype == RS_F32) hipLaunchKernelGGL((maxpool_fwd2_kernel<float, 4>), grid, blk, smem / z, st, p);
+            else hipLaunchKernelGGL((maxpool_fwd2_kernel<bf16_t, 4>), grid, blk, smem / z, st, p);
+        } else {
+            if (dtype == RS_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
+            else hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);
+        }
     } else {
-        const int b = rs_elem_blocks((size_t)(p.D / 2) * (p.H / 2) * (p.W / 2) * CV);
-        if (dtype == RS_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(b, p.N), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(b, p.N), dim3(256), 0, st, p);
+        const size_t items = (size_t)(p.D / 2) * (p.H / 2) * (p.W / 2) * CV;
+        int b = rs_elem_blocks(items), threads = 256;
+        if (rs_glue_variant(-1) && (size_t)b * p.N < 512) { threads = 64; b = (int)((items + 63) / 64); }      // small volumes: one wave per block, four times the CUs
+        if (dtype == RS_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(b, p.N), dim3(threads), 0, st, p);
+        else hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(b, p.N), dim3(threads), 0, st, p);
     }
     return rs_check_launch();
 }
@@ -1248,8 +1521,10 @@ int rs_launch_subsample(const PoolParams& p, int dtype, int bwd, int blocks, hip
     if (CV > 256) return RS_ERR_UNSUPPORTED;
     if (!bwd) {
         const size_t smem = (size_t)(256 / CV) * p.C * 2 * sizeof(float);
-        if (dtype == RS_F32) hipLaunchKernelGGL(subsample_fwd_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
-        else hipLaunchKernelGGL(subsample_fwd_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);
+        const int z = stat_csplit(blocks, p.N, CV);
+        const dim3 grid(blocks, p.N, z), blk(z == 1 ? 256 : (CV / z) * (256 / CV));
+        if (dtype == RS_F32) hipLaunchKernelGGL(subsample_fwd_kernel<float>, grid, blk, smem / z, st, p);
+        else hipLaunchKernelGGL(subsample_fwd_kernel<bf16_t>, grid, blk, smem / z, st, p);
     } else {
         const int b = rs_elem_blocks((size_t)p.D * p.H * p.W * CV);
         if (dtype == RS_F32) hipLaunchKernelGGL(subsample_bwd_kernel<float>, dim3(b, p.N), dim3(256), 0, st, p);
@@ -1296,9 +1571,16 @@ int rs_launch_upsample(const UpParams& p, int dtype, int bwd, int blocks, hipStr
         static const bool v1 = getenv("RSUPER_UPSAMPLE_V1") != nullptr;      // first-generation kernels (A/B, bit-identical results)
         const size_t smem = (size_t)(256 / CV) * p.C * 2 * sizeof(float);
         const bool small = (size_t)p.N * p.ID * p.IH * p.IW * p.ldx < 0x7FFFFFFFull;
+        const size_t tab3 = (size_t)(p.OD + p.OH + p.OW) * sizeof(UpTab);
+        const bool fwd3 = rs_glue_variant(-1) && small && (size_t)p.ID * p.IH * p.IW * p.ldx * (dtype == RS_F32 ? 4 : 2) < 0xFFFFFFFFull && smem + tab3 <= 64 * 1024;
         if (v1 || !small) {
             if (dtype == RS_F32) hipLaunchKernelGGL(upsample_fwd_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
             else hipLaunchKernelGGL(upsample_fwd_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);
+        } else if (fwd3) {                                       // table-driven kernel, channel-split grid on small volumes
+            const int z = stat_csplit(blocks, p.N, CV);
+            const dim3 grid(blocks, p.N, z), blk(z == 1 ? 256 : (CV / z) * (256 / CV));
+            if (dtype == RS_F32) hipLaunchKernelGGL(upsample_fwd3_kernel<float>, grid, blk, smem / z + tab3, st, p);
+            else hipLaunchKernelGGL(upsample_fwd3_kernel<bf16_t>, grid, blk, smem / z + tab3, st, p);
         } else {
             if (dtype == RS_F32) hipLaunchKernelGGL(upsample_fwd2_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
             else hipLaunchKernelGGL(upsample_fwd2_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);

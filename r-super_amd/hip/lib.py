@@ -51,6 +51,7 @@ _SIGS = {
     'rsuper_pointwise_wgrad_splits': (c_int, [c_long, c_int, c_int]),
     'rsuper_pointwise_wgrad': (c_int, [c_int, P, c_int, P, c_int, c_long, c_int, c_int, P, c_int, P, P, P]),
     'rsuper_stats_finalize': (c_int, [P, c_int, c_int, c_int, c_double, c_float, c_int, c_int, P, P]),
+    'rsuper_glue_variant': (c_int, [c_int]),
     'rsuper_in_bwd_finalize': (c_int, [c_int, P, c_int, P, c_int, P, P, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_fwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_bwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
