@@ -525,6 +525,23 @@ long rsuper_largest_component_workspace_bytes(int D, int H, int W);
 int rsuper_largest_component(const void* mask, int is_u8, int D, int H, int W, uint8_t* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Spatial augmentation -- training/augmentation.py random_scale_rotate_translate_3d :228-319 + crop_3d :446-469.
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_AFFINE_MAX_VOLUMES 3
+#define RSUPER_AFFINE_MAX_PLANES 64
+/* F.affine_grid(theta, (B, C, D, H, W), align_corners=True) + F.grid_sample(align_corners=True, padding_mode='zeros') evaluated only on the crop
+ * [oz, oz + d) x [oy, oy + h) x [ox, ox + w) of the full D x H x W output grid (the offset shifts output indices; the transform stays centred on the
+ * full grid).  theta: device [B][3][4] f32, rows x, y, z as affine_grid takes them.  img [B][Ci][D][H][W] f32 -> img_out [B][Ci][d][h][w], trilinear,
+ * every corner tested for bounds.  nvol <= RSUPER_AFFINE_MAX_VOLUMES byte volumes vols[k] [B][planes[k]][D][H][W] u8 -> vols_out[k]
+ * [B][planes[k]][d][h][w], the byte of the nearest voxel (half to even), 0 out of bounds, with the image's coordinates; 1 <= planes[k] <=
+ * RSUPER_AFFINE_MAX_PLANES (bit-packed class planes or plain u8 planes alike).  vols, vols_out, planes: HOST arrays (of device pointers);
+ * offsets: HOST [B][3] ints (z, y, x per sample).  Coordinates are computed in f64.  D, H, W >= 2 (N == 1 has no align-corners coordinate) and
+ * D * H * W < 2^31; the crop must lie inside the grid.  One launch per 8 samples, no workspace. */
+int rsuper_affine_crop(const float* theta, const float* img, float* img_out, int B, int Ci, int D, int H, int W, int nvol,
+                       const uint8_t* const* vols, uint8_t* const* vols_out, const int* planes, int d, int h, int w, const int* offsets,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser -- train_ddp.py:352-357, training/utils.py:46-51,154-161.  host_* are HOST arrays of device pointers.
  * ------------------------------------------------------------------------------------------------ */
 /* *total_sq = sum of squared elements of the n gradient tensors (f64, deterministic order).  The accumulator need not be zeroed: the first launch

@@ -129,6 +129,7 @@ _SIGS = {
     'rsuper_organ_mask_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     'rsuper_largest_component_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_largest_component': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    'rsuper_affine_crop': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),
     'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

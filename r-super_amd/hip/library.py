@@ -17,6 +17,8 @@ loss ops (training/losses_foundation.py; reference call sites rsuper_train/train
 prediction post-processing (inference/detection.py, inference/postprocess.py; no derivative):
     torch.ops.rsuper.detection_volumes(x, out_shape, thresholds, erode) -> (volumes, max_prob)
     torch.ops.rsuper.organ_mask(pred, lesion, organ_a, organ_b) -> planes       torch.ops.rsuper.largest_component(mask) -> mask
+spatial augmentation of the loader (training/augmentation.py; no derivative):
+    torch.ops.rsuper.affine_crop(img, volumes, theta, out_size, offsets) -> (image crop, volume crops)
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -166,3 +168,16 @@ def install_postprocess_ops(detection_volumes, organ_mask, largest_component):
             _register_plain('largest_component', '(Tensor mask, Tensor? workspace=None) -> Tensor', largest_component),
         )
     return _PP_OPS
+
+
+_AUG_OP = None
+
+
+def install_augment_ops(affine_crop):
+    """Register the spatial augmentation operator of training/augmentation.py (on its first use; idempotent) as a plain CUDA kernel: a resampled crop
+    of the loader's input has no derivative."""
+    global _AUG_OP
+    if _AUG_OP is None:
+        _AUG_OP = _register_plain('affine_crop', '(Tensor img, Tensor[] volumes, Tensor theta, int[] out_size, int[] offsets) -> (Tensor, Tensor[])',
+                                  affine_crop)
+    return _AUG_OP

@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from .training import losses_foundation as lf
 from .training.dataset.packed import ingest_packed_batch
+from .training.augmentation import spatial_augment_batch
 from .training.utils import FusedAdamWEMA, ema_alpha_for_step, get_optimizer, exp_lr_scheduler_with_warmup, unwrap_model_checkpoint
 
 
@@ -286,6 +287,9 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
     loss_meters = OrderedDict()
     progress = None
     iter_num_per_epoch = 0
+    aug_gpu = getattr(args, 'aug_device', 'cpu') == 'gpu'
+    if aug_gpu and not packed:
+        raise ValueError('--aug_device gpu resamples the bit-packed volumes: the dataset must deliver packed crops (packed=True)')
     for i, inputs in enumerate(trainLoader):
         batch = dict(image=inputs['image'], label=inputs['label'], unk_channels=inputs['unk_channels'],
                      volumes=inputs['volumes'].float(), mask=inputs['mask'], diameters=inputs['diameters'].float())
@@ -295,6 +299,9 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
             # the three volumes never leave their packed form: the loss kernels read the label bits, the report losses inflate the lesion planes they index
             # and take the unknown map's plane flags from the packed bytes (calculate_loss) -- with and without report supervision
             batch = ingest_packed_batch(batch, len(classes), dev, keep_packed=True)
+            if aug_gpu:     # the reference's random_crop branch on the training stream: random affine + centre crop, or a random plain crop
+                batch['image'], (batch['label'], batch['unk_channels'], batch['mask']) = spatial_augment_batch(
+                    batch['image'], (batch['label'], batch['unk_channels'], batch['mask']), list(args.training_size), args.scale, args.rotate, args.translate)
         else:
             batch = {k: v.to(dev, non_blocking=True) for k, v in batch.items()}
         img = batch['image']
@@ -400,8 +407,13 @@ def get_parser(argv=None, config_root=None):
     parser.add_argument('--load_augmented', action='store_true', help='Loads pre-saved crops for training (:414)')
     parser.add_argument('--save_destination', type=str, default=None, help='directory of the pre-saved crops (:415)')
     parser.add_argument('--hip_graph', action='store_true', help='rsuper_amd extension: replay the training step from a hipGraph (segmentation-only supervision) or the network forward / backward from two graphs around the eager loss (report supervision)')
+    parser.add_argument('--aug_device', type=str, default=None, choices=['cpu', 'gpu'],
+                        help="'gpu': the loader delivers large bit-packed crops (training_size + (20, 40, 40)) and the random affine / crop of the reference's "
+                             "random_crop runs on the device (training/augmentation.py spatial_augment_batch); 'cpu' (default): crops arrive augmented")
     parser.add_argument('--synthetic', type=int, default=0, help='rsuper_amd extension: train on N synthetic samples (no dataset on disk)')
     args = parser.parse_args(argv)
+    if args.aug_device is None:
+        del args.aug_device                  # not given: the YAML value, else 'cpu' below
 
     reports, dr, epochs, ufo_root, w, lr, classes_number = args.reports, args.data_root, args.epochs, args.UFO_root, args.workers, args.lr, args.classes_number
     root = config_root or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config')
@@ -428,11 +440,21 @@ def get_parser(argv=None, config_root=None):
         args.reports = reports
     if args.crop_size is not None:
         args.training_size = [args.crop_size] * 3
-    for k, v in dict(num_workers=0, start_epoch=0, aug_device='cpu', val_freq=10 ** 9).items():
+    # scale / rotate / translate: random_scale_rotate_translate_3d's own defaults where the YAML has none
+    for k, v in dict(num_workers=0, start_epoch=0, aug_device='cpu', val_freq=10 ** 9, scale=0.3, rotate=45, translate=0.1).items():
         if not hasattr(args, k):
             setattr(args, k, v)
     args.batch_size_global = args.batch_size
     return args
+
+
+SOURCE_MARGIN = (20, 40, 40)       # random_crop (dataset_abdomenatlas_UFO.py:569) cuts [d + 20, h + 40, w + 40] before the affine transform
+
+
+def source_size(args):
+    """Extent of the crops the loader delivers: training_size, or with --aug_device gpu the large crop the device augmentation cuts it from."""
+    ts = list(args.training_size)
+    return [t + m for t, m in zip(ts, SOURCE_MARGIN)] if getattr(args, 'aug_device', 'cpu') == 'gpu' else ts
 
 
 def train_net(net, trainset, testset, args, ema_net=None, fold_idx=0, writer=None):
@@ -556,7 +578,9 @@ def main(argv=None):
     from .training.dataset import SyntheticUFODataset, AugmentedCropDataset
     if args.synthetic:
         names = [f'organ_{i}' for i in range(args.classes - 2)] + ['pancreas', 'pancreatic_lesion']
-        trainset = SyntheticUFODataset(sorted(names), size=args.training_size[0], length=args.synthetic)
+        gpu_aug = args.aug_device == 'gpu'
+        trainset = SyntheticUFODataset(sorted(names), size=args.training_size[0], length=args.synthetic, packed=gpu_aug,
+                                       margin=SOURCE_MARGIN if gpu_aug else (0, 0, 0))
     elif args.load_augmented:
         trainset = AugmentedCropDataset.from_directory(args.save_destination, load_label_names(args), packed=True,
                                                        classes_ufo=load_label_names(args, 'UFO_root', required=False))

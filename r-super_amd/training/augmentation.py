@@ -8,9 +8,13 @@ reference draws the same parameters: with the same seeds the outputs agree to fl
 Differences in *how* (not what): the blur is applied as three 1-D passes (k taps each instead of k^3; zero padding makes the
 separable form exact up to rounding -- see gaussian_blur), and gamma / contrast avoid the reference's (C, N) broadcast
 temporaries for the single-channel volumes this path feeds them.
+
+The second half of the file is the spatial augmentation -- random_scale_rotate_translate_3d and crop_3d with the reference's signatures, and
+their fusion for batches of bit-packed volumes (affine_center_crop, spatial_augment_batch) -- on the HIP kernel of csrc/augment.hip.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -97,3 +101,178 @@ def gaussian_blur(img, sigma_range=(0.5, 1.0)):
 def gaussian_noise(img, std, mean=0.0):
     """img + N(0, 1) * std + mean, one draw per voxel (augmentation.py:16-18)."""
     return img + torch.randn(img.shape) * std + mean
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Spatial augmentation on the device (csrc/augment.hip): random_scale_rotate_translate_3d (augmentation.py:228-319) and crop_3d
+# (:446-469), and their fusion for the loader's `random_crop` branch (dataset_abdomenatlas_UFO.py:567-578).  The affine resampling
+# is one HIP launch that reads the f32 image and up to three byte volumes (bit-packed class planes or plain u8 planes) with the
+# same coordinates and writes only the output crop.  No CPU kernel: a CPU tensor raises RSuperHipError.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _triple(v):
+    return [v] * 3 if isinstance(v, (float, int)) else list(v)
+
+
+def draw_affine_3d(scale=0.3, rotate=45, translate=0.1, shear=0.05):
+    """The (3, 4) float32 theta of random_scale_rotate_translate_3d (:236-288).  Consumes np.random in the reference's order --
+    three scales U(1 - s, 1 / (1 - s)), six shears, three translations, three integer angles randint(-r, max(r, 1)) -- and
+    composes Rx . Ry . Rz . S as float32 torch.mm products in the same order: with the same seed theta is bit-identical.
+    Arguments as the reference takes them: scalars or per-axis lists."""
+    scale, translate, rotate, shear = _triple(scale), _triple(translate), _triple(rotate), _triple(shear)
+    u = np.random.uniform
+    scale_x, scale_y, scale_z = (u(low=1 - s, high=1 / (1 - s)) for s in scale)
+    shear_xy, shear_xz = u(-shear[0], shear[0]), u(-shear[0], shear[0])
+    shear_yx, shear_yz = u(-shear[1], shear[1]), u(-shear[1], shear[1])
+    shear_zx, shear_zy = u(-shear[2], shear[2]), u(-shear[2], shear[2])
+    translate_x, translate_y, translate_z = (u(-t, t) for t in translate)
+    theta_scale = torch.tensor([[scale_x, shear_xy, shear_xz, translate_x],
+                                [shear_yx, scale_y, shear_yz, translate_y],
+                                [shear_zx, shear_zy, scale_z, translate_z],
+                                [0, 0, 0, 1]]).float()
+    ax, ay, az = ((float(np.random.randint(-r, max(r, 1))) / 180.) * math.pi for r in rotate)
+    rx = torch.tensor([[1, 0, 0, 0], [0, math.cos(ax), -math.sin(ax), 0], [0, math.sin(ax), math.cos(ax), 0], [0, 0, 0, 1]]).float()
+    ry = torch.tensor([[math.cos(ay), 0, -math.sin(ay), 0], [0, 1, 0, 0], [math.sin(ay), 0, math.cos(ay), 0], [0, 0, 0, 1]]).float()
+    rz = torch.tensor([[math.cos(az), -math.sin(az), 0, 0], [math.sin(az), math.cos(az), 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]]).float()
+    theta = torch.mm(torch.mm(rx, ry), rz)
+    return torch.mm(theta, theta_scale)[0:3, :]
+
+
+IDENTITY_THETA = ((1., 0., 0., 0.), (0., 1., 0., 0.), (0., 0., 1., 0.))
+
+
+def _affine_crop(img, volumes, theta, out_size, offsets):
+    """The C ABI call.  img (B, Ci, D, H, W) f32, volumes: list of (B, P, D, H, W) u8, theta (B, 3, 4) f32 (any device: it is
+    12 floats per sample), offsets: B * 3 ints (z, y, x per sample) -> (image crop, list of volume crops)."""
+    import ctypes
+    from ..hip import lib as _l
+    if not img.is_cuda or any(not v.is_cuda for v in volumes):
+        raise _l.RSuperHipError('affine_crop needs device tensors (no CPU fallback)')
+    if img.dim() != 5 or img.dtype != torch.float32:
+        raise ValueError('affine_crop: image must be float32 (B, Ci, D, H, W), got %s %s' % (img.dtype, tuple(img.shape)))
+    B, Ci, D, H, W = img.shape
+    d, h, w = (int(s) for s in out_size)
+    for v in volumes:
+        if v.dtype != torch.uint8 or v.dim() != 5 or v.shape[0] != B or tuple(v.shape[2:]) != (D, H, W):
+            raise ValueError('affine_crop: byte volumes must be uint8 (B, P, D, H, W) on the image grid')
+    if tuple(theta.shape) != (B, 3, 4):
+        raise ValueError('affine_crop: theta must be (B, 3, 4)')
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != 3 * B:
+        raise ValueError('affine_crop: one (z, y, x) offset per sample')
+    img = img.contiguous()
+    volumes = [v.contiguous() for v in volumes]
+    theta = theta.to(device=img.device, dtype=torch.float32).contiguous()
+    out = torch.empty((B, Ci, d, h, w), device=img.device, dtype=torch.float32)
+    outs = [torch.empty((B, v.shape[1], d, h, w), device=img.device, dtype=torch.uint8) for v in volumes]
+    n = len(volumes)
+    src = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in volumes])
+    dst = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in outs])
+    planes = (ctypes.c_int * max(n, 1))(*[v.shape[1] for v in volumes])
+    offs = (ctypes.c_int * (3 * B))(*offsets)
+    with torch.cuda.device(img.device):
+        _l.check(_l.lib().rsuper_affine_crop(theta.data_ptr(), img.data_ptr(), out.data_ptr(), B, Ci, D, H, W, n, src, dst, planes, d, h, w, offs,
+                                             torch.cuda.current_stream().cuda_stream), 'affine_crop')
+    return out, outs
+
+
+def _affine_crop_op(img, volumes, theta, out_size, offsets):
+    """torch.ops.rsuper.affine_crop, registered on first use (hip/library.py); no derivative."""
+    from ..hip import lib as _l
+    from ..hip import ops as _ops          # noqa: F401  (hip/ops.py pulls in hip/library.py; this order avoids the import cycle)
+    from ..hip import library as _library
+    if not img.is_cuda:                                    # the dispatcher's "no CPU kernel" error, as the project's own exception
+        raise _l.RSuperHipError('affine_crop needs device tensors (no CPU fallback)')
+    return _library.install_augment_ops(_affine_crop)(img, list(volumes), theta, list(out_size), list(offsets))
+
+
+def crop_3d(img, lab, crop_size, mode):
+    """crop_3d (:446-469): 'random' draws np.random.randint(0, max(diff, 1)) for z, y, x in this order, 'center' takes diff // 2."""
+    assert mode in ['random', 'center'], "Invalid Mode, should be 'random' or 'center'"
+    if isinstance(crop_size, int):
+        crop_size = [crop_size] * 3
+    z, y, x = crop_offsets(img.shape[2:], crop_size, mode)
+    cd, ch, cw = crop_size
+    return img[:, :, z:z + cd, y:y + ch, x:x + cw].contiguous(), lab[:, :, z:z + cd, y:y + ch, x:x + cw].contiguous()
+
+
+def crop_offsets(size, crop_size, mode):
+    """The (z, y, x) corner crop_3d cuts at (:453-464)."""
+    diff = [int(s) - int(c) for s, c in zip(size, crop_size)]
+    if mode == 'random':
+        return [int(np.random.randint(0, max(df, 1))) for df in diff]
+    return [df // 2 for df in diff]
+
+
+def _as_bytes(t, what):
+    """int64 / u8 / bool volume -> the u8 planes the kernel gathers (the reference resamples .float() planes with 'nearest': values pass through)."""
+    if t.dtype in (torch.uint8, torch.bool):
+        return t.to(torch.uint8)
+    if t.dtype == torch.int64:
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) > 255):
+            raise ValueError('%s: label values must fit a byte' % what)
+        return t.to(torch.uint8)
+    raise ValueError('%s: expected an int64, uint8 or bool volume, got %s' % (what, t.dtype))
+
+
+def random_scale_rotate_translate_3d(img, lab, scale=0.3, rotate=45, translate=0.1, shear=0.05, foreground=None):
+    """random_scale_rotate_translate_3d (:228-319) on device tensors: img (1, C, D, H, W) f32 trilinear, lab (1, C, D, H, W) int64 / u8 / bool
+    nearest -> int64 as the reference's `.long()`, foreground (D, H, W) / (1, D, H, W) / (1, 1, D, H, W) nearest -> bool in its own rank.
+    The kernel runs with the crop set to the full volume."""
+    assert len(img.size()) == 5
+    theta = draw_affine_3d(scale, rotate, translate, shear)
+    B = img.shape[0]
+    vols = [_as_bytes(lab, 'lab')]
+    if foreground is not None:
+        if foreground.ndim not in (3, 4, 5):
+            raise ValueError('Invalid dimension of foreground mask')
+        fg = _as_bytes(foreground, 'foreground')
+        vols.append(fg.reshape((1,) * (5 - fg.ndim) + tuple(fg.shape)))
+    out, outs = _affine_crop_op(img.float(), vols, theta.unsqueeze(0).expand(B, 3, 4), img.shape[2:], [0, 0, 0] * B)
+    if foreground is None:
+        return out, outs[0].long()
+    return out, outs[0].long(), outs[1].reshape(foreground.shape).bool()
+
+
+def _packed_of(v):
+    return v.packed if hasattr(v, 'packed') else v
+
+
+def _like(v, t):
+    return type(v)(t, v.C) if hasattr(v, 'packed') else t
+
+
+def affine_center_crop(img, volumes, theta, out_size):
+    """The fused production path: img (B, Ci, D, H, W) f32, volumes: tuple of packed u8 (B, P, D, H, W) tensors or PackedBits, theta (B, 3, 4) ->
+    (image crop, tuple of crops of the same kinds).  Equals transforming the whole volume and then crop_3d(..., 'center') -- offsets
+    ((D - d) // 2, (H - h) // 2, (W - w) // 2) -- but only the crop is computed."""
+    off = crop_offsets(img.shape[2:], out_size, 'center')
+    out, outs = _affine_crop_op(img, [_packed_of(v) for v in volumes], theta, out_size, off * img.shape[0])
+    return out, tuple(_like(v, t) for v, t in zip(volumes, outs))
+
+
+def plan_spatial_augment(batch, size, training_size, scale, rotate, translate, p=0.4):
+    """The random draws of `random_crop` (dataset_abdomenatlas_UFO.py:573-577) for `batch` samples of extent `size`, in the reference's order per
+    sample: np.random.random() < p -> the affine draws, centre crop; otherwise the three randint offsets of a random plain crop (identity theta).
+    Returns theta (batch, 3, 4) f32, the flat offset list and the branch taken per sample (True = affine)."""
+    thetas, offs, branch = [], [], []
+    for _ in range(batch):
+        if np.random.random() < p:
+            thetas.append(draw_affine_3d(scale, rotate, translate))
+            offs += crop_offsets(size, training_size, 'center')
+            branch.append(True)
+        else:
+            thetas.append(torch.tensor(IDENTITY_THETA))
+            offs += crop_offsets(size, training_size, 'random')
+            branch.append(False)
+    return torch.stack(thetas), offs, branch
+
+
+def spatial_augment_batch(img, volumes, training_size, scale, rotate, translate, p=0.4):
+    """`random_crop`'s branch for a batch of large crops (d + 20, h + 40, w + 40) already on the device: per sample, with probability p the random
+    affine + centre crop, otherwise a random plain crop to training_size -- the same kernel with an identity theta (an exact copy) and that
+    sample's offset, so the whole batch is one launch.  volumes as in affine_center_crop."""
+    if isinstance(training_size, int):
+        training_size = [training_size] * 3
+    theta, offs, _ = plan_spatial_augment(img.shape[0], img.shape[2:], training_size, scale, rotate, translate, p)
+    out, outs = _affine_crop_op(img, [_packed_of(v) for v in volumes], theta, training_size, offs)
+    return out, tuple(_like(v, t) for v, t in zip(volumes, outs))

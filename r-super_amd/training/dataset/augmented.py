@@ -18,7 +18,9 @@ device by `ingest_packed_batch` (packed.py); with `packed=False` they are unpack
 
 Out of scope (offline preprocessing): building the crops from NIfTI volumes (`__getitem__`'s crop-on-tumor path,
 `define_unknown_voxels`, `get_chosen_segment_mask`).  A report sample whose side files are missing therefore raises instead
-of being regenerated.
+of being regenerated.  The random affine + crop of `random_crop` (:567-578) is not part of that: a directory of LARGE crops
+(training_size + (20, 40, 40)) read with `packed=True` is transformed on the device, `train_ddp --aug_device gpu`
+(training/augmentation.py spatial_augment_batch).
 """
 import json
 import math
