@@ -525,6 +525,30 @@ long rsuper_largest_component_workspace_bytes(int D, int H, int W);
 int rsuper_largest_component(const void* mask, int is_u8, int D, int H, int W, uint8_t* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Validation metrics -- metric/metrics.py compute_surface_distances :265-573.  Masks of up to 2^31 corners ((D+1) * (H+1) * (W+1)).
+ * No call issues a memset: counters and bounds are initialised by the call's own kernels.
+ * ------------------------------------------------------------------------------------------------ */
+/* Neighbour codes of two mask stacks gt, pred [planes][D][H][W] (u8, non-zero = foreground) on the corner grid: codes_*[planes][D+1][H+1][W+1] =
+ * correlate(mask, [[[128, 64], [32, 16]], [[8, 4], [2, 1]]], mode='constant'), corner (i, j, k) seeing voxels i-1..i, j-1..j, k-1..k and zero outside.
+ * bbox: device [planes][6] i32 = min z, y, x and max z, y, x of the corners whose code is a border code (neither 0 nor 255) in either mask
+ * (min > max when there is none).  counts: device [planes][5] i64 = |gt|, |pred|, |gt & pred|, border corners of gt, border corners of pred. */
+int rsuper_surface_codes(const uint8_t* gt, const uint8_t* pred, int planes, int D, int H, int W, uint8_t* codes_gt, uint8_t* codes_pred,
+                         int* bbox, long long* counts, void* stream);
+/* Exact squared Euclidean distance transform, distance_transform_edt(~borders, sampling=(s0, s1, s2)) ** 2 in f64, of the sub-box
+ * [z0, z0 + nz) x [y0, y0 + ny) x [x0, x0 + nx) of one code volume codes[Dc][Hc][Wc] to the border corners inside the box: out[nz][ny][nx].
+ * Separable: a wave-level scan along W, then a lower envelope per line along H and D (Felzenszwalb-Huttenlocher) whose stacks live in the
+ * workspace (rsuper_edt3_workspace_bytes(nz, ny, nx) bytes on the device; 0 = unsupported box: a side above 4096 corners or more than 2^31
+ * corners).  A box without a border corner gives +inf everywhere.  workspace_bytes below the requirement is refused with RSUPER_ERR_ARG. */
+long rsuper_edt3_workspace_bytes(int nz, int ny, int nx);
+int rsuper_edt3(const uint8_t* codes, int Dc, int Hc, int Wc, int z0, int y0, int x0, int nz, int ny, int nx, double s0, double s1, double s2,
+                double* out, void* workspace, long workspace_bytes, void* stream);
+/* For every border corner of codes[Dc][Hc][Wc] inside the box: dist = sqrt(sqdist[box index]) (sqdist NULL: +inf, the other mask has no surface),
+ * area = table[code] (table: device [256] f64), compacted into dist / area [capacity] in an order that is not fixed (the caller sorts the pairs);
+ * *count (device i64) = number of border corners in the box.  Pairs beyond capacity are counted, not written. */
+int rsuper_surfel_gather(const uint8_t* codes, int Dc, int Hc, int Wc, int z0, int y0, int x0, int nz, int ny, int nx, const double* sqdist,
+                         const double* table, double* dist, double* area, long long* count, long capacity, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Spatial augmentation -- training/augmentation.py random_scale_rotate_translate_3d :228-319 + crop_3d :446-469.
  * ------------------------------------------------------------------------------------------------ */
 #define RSUPER_AFFINE_MAX_VOLUMES 3

@@ -130,6 +130,10 @@ _SIGS = {
     'rsuper_largest_component_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_largest_component': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     'rsuper_affine_crop': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),
+    'rsuper_surface_codes': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    'rsuper_edt3_workspace_bytes': (c_long, [c_int, c_int, c_int]),
+    'rsuper_edt3': (c_int, [P] + [c_int] * 9 + [c_double] * 3 + [P, P, c_long, P]),
+    'rsuper_surfel_gather': (c_int, [P] + [c_int] * 9 + [P, P, P, P, P, c_long, P]),
     'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

@@ -19,6 +19,9 @@ prediction post-processing (inference/detection.py, inference/postprocess.py; no
     torch.ops.rsuper.organ_mask(pred, lesion, organ_a, organ_b) -> planes       torch.ops.rsuper.largest_component(mask) -> mask
 spatial augmentation of the loader (training/augmentation.py; no derivative):
     torch.ops.rsuper.affine_crop(img, volumes, theta, out_size, offsets) -> (image crop, volume crops)
+validation metrics (metric/metrics.py; no derivative):
+    torch.ops.rsuper.surface_distances(mask_gt, mask_pred, spacing, area_table) -> (sorted distances and areas per plane, counts)
+    torch.ops.rsuper.edt3(codes, box, spacing, workspace) -> squared distances
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -181,3 +184,19 @@ def install_augment_ops(affine_crop):
         _AUG_OP = _register_plain('affine_crop', '(Tensor img, Tensor[] volumes, Tensor theta, int[] out_size, int[] offsets) -> (Tensor, Tensor[])',
                                   affine_crop)
     return _AUG_OP
+
+
+_METRIC_OPS = None
+
+
+def install_metric_ops(surface_distances, edt3):
+    """Register the validation-metric operators of metric/metrics.py (at the end of that module's setup; idempotent) as plain CUDA kernels:
+    distances between mask surfaces have no derivative."""
+    global _METRIC_OPS
+    if _METRIC_OPS is None:
+        _METRIC_OPS = (
+            _register_plain('surface_distances', '(Tensor mask_gt, Tensor mask_pred, float[] spacing, Tensor area_table) -> (Tensor[], Tensor)',
+                            surface_distances),
+            _register_plain('edt3', '(Tensor codes, int[] box, float[] spacing, Tensor? workspace=None) -> Tensor', edt3),
+        )
+    return _METRIC_OPS

@@ -460,7 +460,10 @@ def source_size(args):
 def train_net(net, trainset, testset, args, ema_net=None, fold_idx=0, writer=None):
     """Training half of train_net (train_ddp.py:65-232): ChunkedSampler + DataLoader (:105-123), optimizer (:141), per epoch
     the sampler reshuffle, the exponential warm-up / polynomial LR schedule (:170) and train_epoch, the `latest` checkpoint of
-    every epoch and the numbered one every 25 (:181-200).  Validation (:203-230) is outside the hot path."""
+    every epoch and the numbered one every 25 (:181-200).  Every args.val_freq epochs (:201-225; the default never comes), when a test set is
+    given, the EMA network (args.ema) or the network is validated on the device (training/validation.py), the per-class Dice / ASD / HD are
+    logged and the `_best` checkpoint follows the mean Dice as in the reference (>=, so a tie moves it).  Returns the per-epoch meter history;
+    the best (dice, ASD, HD) triple is kept in args.best_validation."""
     from torch.utils import data
     from .training.dataset import ChunkedSampler
     leng = len(trainset.img_list) if hasattr(trainset, 'img_list') else len(trainset)
@@ -477,6 +480,11 @@ def train_net(net, trainset, testset, args, ema_net=None, fold_idx=0, writer=Non
     if args.epochs is None:
         raise ValueError('--epochs is required: argparse defines the attribute, so the YAML value never fills it (train_ddp.py:491-502)')
     history = []
+    test_loader = None
+    val_freq = getattr(args, 'val_freq', 10 ** 9)
+    if testset is not None and val_freq <= args.epochs:
+        test_loader = data.DataLoader(testset, batch_size=1, shuffle=False, num_workers=0)
+    best = None
     for epoch in range(args.start_epoch, args.epochs):
         sampler.set_epoch(epoch)
         lr = exp_lr_scheduler_with_warmup(optimizer, epoch=epoch, warmup_epoch=args.warmup, max_epoch=args.epochs)
@@ -488,6 +496,22 @@ def train_net(net, trainset, testset, args, ema_net=None, fold_idx=0, writer=Non
             save_checkpoint(os.path.join(cp_dir, f'fold_{fold_idx}_latest.pth'), epoch, net, ema_net, optimizer, args)
             if (epoch + 1) % 25 == 0:
                 save_checkpoint(os.path.join(cp_dir, f'fold_{fold_idx}_epoch_{epoch + 1}.pth'), epoch, net, ema_net, optimizer, args)
+        if test_loader is not None and (epoch + 1) % val_freq == 0 and not getattr(args, 'clip_pretrain', False):
+            from .training.validation import validation
+            net_for_eval = ema_net if (getattr(args, 'ema', False) and ema_net is not None) else net
+            net_for_eval = getattr(net_for_eval, 'module', net_for_eval)
+            dice_v, asd_v, hd_v = validation(net_for_eval, test_loader, args, matcher=None)
+            net.train()
+            if is_master(args):
+                names = list(getattr(testset, 'classes', None) or getattr(trainset, 'classes', None) or range(len(dice_v)))
+                for n, d, a, h in zip(names, dice_v, asd_v, hd_v):
+                    logging.info(f'  {n}: Dice {d:.4f}  ASD {a:.3f}  HD {h:.3f}')
+                if best is None or np.nanmean(dice_v) >= np.nanmean(best[0]):
+                    best = (dice_v, asd_v, hd_v)
+                    save_checkpoint(os.path.join(cp_dir, f'fold_{fold_idx}_best.pth'), epoch, net, ema_net, optimizer, args)
+                logging.info('Evaluation Done')
+                logging.info(f'Dice: {np.nanmean(dice_v):.4f}/Best Dice: {np.nanmean(best[0]):.4f}')
+                args.best_validation = best
     return history
 
 
