@@ -566,6 +566,29 @@ int rsuper_affine_crop(const float* theta, const float* img, float* img_out, int
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Intensity augmentation -- training/augmentation.py brightness_multiply / brightness_additive / gamma / contrast / gaussian_blur /
+ * gaussian_noise :27-103, gated per sample as dataset/augmented.py online_intensity_augmentation :142-158.
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_BLUR_MAX_RADIUS 5
+/* img [B][1][D][H][W] f32 -> out (another buffer of the same shape; img is not modified).  Per sample b, HOST arrays: flags[b] = bit 0 multiply, 1 additive,
+ * 2 gamma, 3 contrast, 4 blur, 5 noise (the transforms that fired; they apply in this order); scalars[b][5] = multiply factor, additive offset, gamma
+ * exponent, contrast factor, noise std; radius[b] and taps[b][2 * RSUPER_BLUR_MAX_RADIUS + 1] (the first 2 * radius + 1 are read) for the zero-padded
+ * separable blur W -> H -> D of the post-contrast image; seeds[b] = the Philox4x32-10 key of the in-kernel N(0, 1) field (counter (i >> 2, 0, 0) for voxel
+ * i of the sample, two Box-Muller pairs, voxel i takes normal i & 3).  noise: optional device [B][1][D][H][W] f32 that replaces the generator.
+ * gamma: lo, hi, mean, unbiased std of x2 = x * f + a; y = pow((x2 - lo) / (hi - lo), g) * (hi - lo) + lo; z = (y - mean y) / std y * std + mean (a
+ * constant volume gives NaN, as the host code does).  contrast: clamp((v - mean) * c + mean, lo, hi) with lo, hi, mean of its input -- after gamma
+ * they are z(min y), z(max y) and gamma's restored mean.  The reductions go through per-block partials in `workspace` (device,
+ * rsuper_intensity_augment_workspace_bytes(B, D, H, W) bytes; needed when gamma or contrast fires anywhere; 0 = an empty shape) combined in a fixed
+ * order: no atomics, no memset, bit-reproducible.  rsuper_intensity_augment_launches: kernel launches the call makes for these flags (per group of 8
+ * samples: 1, +1 with contrast or gamma, +1 with gamma).  A blur radius above RSUPER_BLUR_MAX_RADIUS, flags outside 0..63, D * H * W >= 2^31 or a missing /
+ * short workspace -> RSUPER_ERR_ARG. */
+long rsuper_intensity_augment_workspace_bytes(int B, int D, int H, int W);
+int rsuper_intensity_augment_launches(int B, const int* flags);
+int rsuper_intensity_augment(const float* img, float* out, int B, int D, int H, int W, const int* flags, const float* scalars, const int* radius,
+                             const float* taps, const unsigned long long* seeds, const float* noise, void* workspace, long workspace_bytes,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser -- train_ddp.py:352-357, training/utils.py:46-51,154-161.  host_* are HOST arrays of device pointers.
  * ------------------------------------------------------------------------------------------------ */
 /* *total_sq = sum of squared elements of the n gradient tensors (f64, deterministic order).  The accumulator need not be zeroed: the first launch

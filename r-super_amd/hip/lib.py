@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(os.path.dirname(_HERE), 'csrc', 'librsuper_hip.so')
 
 F32, BF16 = 0, 1
+BLUR_MAX_RADIUS = 5        # RSUPER_BLUR_MAX_RADIUS of the header: rsuper_intensity_augment takes 2 * BLUR_MAX_RADIUS + 1 taps per sample
 _LIB = None
 
 P = c_void_p
@@ -130,6 +131,9 @@ _SIGS = {
     'rsuper_largest_component_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_largest_component': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     'rsuper_affine_crop': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),
+    'rsuper_intensity_augment_workspace_bytes': (c_long, [c_int] * 4),
+    'rsuper_intensity_augment_launches': (c_int, [c_int, P]),
+    'rsuper_intensity_augment': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_long, P]),
     'rsuper_surface_codes': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     'rsuper_edt3_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_edt3': (c_int, [P] + [c_int] * 9 + [c_double] * 3 + [P, P, c_long, P]),

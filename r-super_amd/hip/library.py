@@ -19,6 +19,8 @@ prediction post-processing (inference/detection.py, inference/postprocess.py; no
     torch.ops.rsuper.organ_mask(pred, lesion, organ_a, organ_b) -> planes       torch.ops.rsuper.largest_component(mask) -> mask
 spatial augmentation of the loader (training/augmentation.py; no derivative):
     torch.ops.rsuper.affine_crop(img, volumes, theta, out_size, offsets) -> (image crop, volume crops)
+intensity augmentation of the loader (training/augmentation.py; no derivative):
+    torch.ops.rsuper.intensity_augment(img, flags, scalars, radius, taps, seeds, noise, workspace) -> img
 validation metrics (metric/metrics.py; no derivative):
     torch.ops.rsuper.surface_distances(mask_gt, mask_pred, spacing, area_table) -> (sorted distances and areas per plane, counts)
     torch.ops.rsuper.edt3(codes, box, spacing, workspace) -> squared distances
@@ -184,6 +186,19 @@ def install_augment_ops(affine_crop):
         _AUG_OP = _register_plain('affine_crop', '(Tensor img, Tensor[] volumes, Tensor theta, int[] out_size, int[] offsets) -> (Tensor, Tensor[])',
                                   affine_crop)
     return _AUG_OP
+
+
+_INTENSITY_OP = None
+
+
+def install_intensity_ops(intensity_augment):
+    """Register the intensity augmentation operator of training/augmentation.py (on its first use; idempotent) as a plain CUDA kernel: the loader's
+    input has no derivative.  seeds are the 64-bit Philox keys as signed ints (the schema has no unsigned type)."""
+    global _INTENSITY_OP
+    if _INTENSITY_OP is None:
+        _INTENSITY_OP = _register_plain('intensity_augment', '(Tensor img, int[] flags, float[] scalars, int[] radius, float[] taps, int[] seeds, '
+                                        'Tensor? noise=None, Tensor? workspace=None) -> Tensor', intensity_augment)
+    return _INTENSITY_OP
 
 
 _METRIC_OPS = None

@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from .training import losses_foundation as lf
 from .training.dataset.packed import ingest_packed_batch
-from .training.augmentation import spatial_augment_batch
+from .training.augmentation import spatial_augment_batch, intensity_augment_batch
 from .training.utils import FusedAdamWEMA, ema_alpha_for_step, get_optimizer, exp_lr_scheduler_with_warmup, unwrap_model_checkpoint
 
 
@@ -288,6 +288,7 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
     progress = None
     iter_num_per_epoch = 0
     aug_gpu = getattr(args, 'aug_device', 'cpu') == 'gpu'
+    intensity_gpu = getattr(args, 'intensity_aug_device', 'cpu') == 'gpu'
     if aug_gpu and not packed:
         raise ValueError('--aug_device gpu resamples the bit-packed volumes: the dataset must deliver packed crops (packed=True)')
     for i, inputs in enumerate(trainLoader):
@@ -299,11 +300,15 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
             # the three volumes never leave their packed form: the loss kernels read the label bits, the report losses inflate the lesion planes they index
             # and take the unknown map's plane flags from the packed bytes (calculate_loss) -- with and without report supervision
             batch = ingest_packed_batch(batch, len(classes), dev, keep_packed=True)
+            if intensity_gpu:   # the reference's order: the six intensity transforms on the crop as loaded, then the affine transform / crop
+                batch['image'] = intensity_augment_batch(batch['image'])
             if aug_gpu:     # the reference's random_crop branch on the training stream: random affine + centre crop, or a random plain crop
                 batch['image'], (batch['label'], batch['unk_channels'], batch['mask']) = spatial_augment_batch(
                     batch['image'], (batch['label'], batch['unk_channels'], batch['mask']), list(args.training_size), args.scale, args.rotate, args.translate)
         else:
             batch = {k: v.to(dev, non_blocking=True) for k, v in batch.items()}
+            if intensity_gpu:
+                batch['image'] = intensity_augment_batch(batch['image'])
         img = batch['image']
         step = i + epoch * len(trainLoader)                      # global steps (:306)
         if lf.SANITY_CHECKS and guard is not None:               # the same three asserts (:311-313) as device flags, raised by guard.poll()
@@ -410,10 +415,15 @@ def get_parser(argv=None, config_root=None):
     parser.add_argument('--aug_device', type=str, default=None, choices=['cpu', 'gpu'],
                         help="'gpu': the loader delivers large bit-packed crops (training_size + (20, 40, 40)) and the random affine / crop of the reference's "
                              "random_crop runs on the device (training/augmentation.py spatial_augment_batch); 'cpu' (default): crops arrive augmented")
+    parser.add_argument('--intensity_aug_device', type=str, default=None, choices=['cpu', 'gpu'],
+                        help="'gpu': the loader delivers crops without the six online intensity transforms and they run on the device, per sample, before "
+                             "the spatial augmentation (training/augmentation.py intensity_augment_batch); 'cpu' (default): the loader's workers apply them")
     parser.add_argument('--synthetic', type=int, default=0, help='rsuper_amd extension: train on N synthetic samples (no dataset on disk)')
     args = parser.parse_args(argv)
     if args.aug_device is None:
         del args.aug_device                  # not given: the YAML value, else 'cpu' below
+    if args.intensity_aug_device is None:
+        del args.intensity_aug_device        # likewise
 
     reports, dr, epochs, ufo_root, w, lr, classes_number = args.reports, args.data_root, args.epochs, args.UFO_root, args.workers, args.lr, args.classes_number
     root = config_root or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config')
@@ -441,7 +451,7 @@ def get_parser(argv=None, config_root=None):
     if args.crop_size is not None:
         args.training_size = [args.crop_size] * 3
     # scale / rotate / translate: random_scale_rotate_translate_3d's own defaults where the YAML has none
-    for k, v in dict(num_workers=0, start_epoch=0, aug_device='cpu', val_freq=10 ** 9, scale=0.3, rotate=45, translate=0.1).items():
+    for k, v in dict(num_workers=0, start_epoch=0, aug_device='cpu', intensity_aug_device='cpu', val_freq=10 ** 9, scale=0.3, rotate=45, translate=0.1).items():
         if not hasattr(args, k):
             setattr(args, k, v)
     args.batch_size_global = args.batch_size
@@ -606,7 +616,8 @@ def main(argv=None):
         trainset = SyntheticUFODataset(sorted(names), size=args.training_size[0], length=args.synthetic, packed=gpu_aug,
                                        margin=SOURCE_MARGIN if gpu_aug else (0, 0, 0))
     elif args.load_augmented:
-        trainset = AugmentedCropDataset.from_directory(args.save_destination, load_label_names(args), packed=True,
+        # --intensity_aug_device gpu: the workers only read files, the six intensity transforms run in train_epoch
+        trainset = AugmentedCropDataset.from_directory(args.save_destination, load_label_names(args), packed=True, augment=args.intensity_aug_device != 'gpu',
                                                        classes_ufo=load_label_names(args, 'UFO_root', required=False))
     else:
         raise SystemExit('rsuper_amd.train_ddp trains from pre-saved crops: pass --load_augmented --save_destination DIR '

@@ -276,3 +276,162 @@ def spatial_augment_batch(img, volumes, training_size, scale, rotate, translate,
     theta, offs, _ = plan_spatial_augment(img.shape[0], img.shape[2:], training_size, scale, rotate, translate, p)
     out, outs = _affine_crop_op(img, [_packed_of(v) for v in volumes], theta, training_size, offs)
     return out, tuple(_like(v, t) for v, t in zip(volumes, outs))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Intensity augmentation on the device (csrc/augment_intensity.hip): the six functions at the top of this file, gated per sample as
+# dataset/augmented.py online_intensity_augmentation gates them, for a batch of (B, 1, D, H, W) volumes already on the training stream.
+# A plan holds what fired and with which parameter per sample; one C ABI call applies it (at most 3 launches per 8 samples).
+# No CPU kernel: a CPU tensor raises RSuperHipError.
+# ---------------------------------------------------------------------------------------------------------------------------
+INTENSITY_TRANSFORMS = ('multiply', 'additive', 'gamma', 'contrast', 'blur', 'noise')      # bit k of a sample's flags = transform k fired
+
+
+class IntensityPlan:
+    """Per sample: flags (bit k = INTENSITY_TRANSFORMS[k] fired), the four scalars and the noise std as exact float32 values (0 where not fired),
+    sigma / radius / taps of the blur (taps: the 2 * radius + 1 float32 values of gaussian_kernel_1d) and the 64-bit noise seed."""
+
+    def __init__(self, batch):
+        self.batch = batch
+        self.flags = [0] * batch
+        self.multiply, self.additive, self.gamma, self.contrast, self.noise_std = ([0.0] * batch for _ in range(5))
+        self.sigma, self.radius, self.taps = [None] * batch, [0] * batch, [[] for _ in range(batch)]
+        self.seed = [0] * batch
+
+    def fired(self, b):
+        return [n for k, n in enumerate(INTENSITY_TRANSFORMS) if self.flags[b] >> k & 1]
+
+
+def _f32(v):
+    """The float32 value of a Python number / one-element tensor, as an (exact) Python float."""
+    return float(torch.as_tensor(v, dtype=torch.float32).reshape(-1)[0])
+
+
+def _per_sample(v, batch, what):
+    if v is None:
+        return [None] * batch
+    v = list(v)
+    if len(v) != batch:
+        raise ValueError('%s: one value (or None) per sample, got %d for a batch of %d' % (what, len(v), batch))
+    return v
+
+
+def make_intensity_plan(batch, multiply=None, additive=None, gamma=None, contrast=None, sigma=None, noise_std=None, seed=None):
+    """A plan from explicit per-sample values: every argument is None or a sequence of `batch` entries, an entry None = that transform did not fire
+    for that sample.  sigma becomes the radius ceil(3 sigma) and the taps of gaussian_kernel_1d exactly as gaussian_blur computes them (float32
+    sigma, kernel size 2 * ceil(3 sigma) + 1).  seed: the 64-bit key of the in-kernel noise field per sample (default 0; unused with an explicit
+    noise tensor)."""
+    plan = IntensityPlan(batch)
+    cols = [_per_sample(v, batch, n) for v, n in ((multiply, 'multiply'), (additive, 'additive'), (gamma, 'gamma'), (contrast, 'contrast'),
+                                                  (sigma, 'sigma'), (noise_std, 'noise_std'))]
+    seeds = _per_sample(seed, batch, 'seed')
+    for b in range(batch):
+        for k, dst in ((0, plan.multiply), (1, plan.additive), (2, plan.gamma), (3, plan.contrast), (5, plan.noise_std)):
+            if cols[k][b] is not None:
+                plan.flags[b] |= 1 << k
+                dst[b] = _f32(cols[k][b])
+        if cols[4][b] is not None:
+            s = torch.as_tensor(cols[4][b], dtype=torch.float32).reshape(1)
+            ks = 2 * math.ceil(3 * s) + 1
+            plan.flags[b] |= 1 << 4
+            plan.sigma[b], plan.radius[b], plan.taps[b] = float(s), ks // 2, [float(t) for t in gaussian_kernel_1d(ks, s)]
+        if seeds[b] is not None:
+            plan.seed[b] = int(seeds[b]) & 0xFFFFFFFFFFFFFFFF
+    return plan
+
+
+def plan_intensity_augment(batch, p=0.3, multiply_range=(0.7, 1.3), additive_std=0.1, gamma_range=(0.7, 1.5), contrast_range=(0.7, 1.3),
+                           sigma_range=(0.5, 1.5), noise_std_max=0.2):
+    """The random draws of online_intensity_augmentation plus the six functions for `batch` samples, from numpy's and torch's global generators in
+    the reference's order and shapes per sample: the gate np.random.random() < p, then the transform's own torch.rand / torch.normal
+    ((1, 1, 1, 1, 1) for multiply and additive, (1, 1) for gamma and contrast, (1,) for sigma); for the noise the gate, then np.random.random() *
+    noise_std_max.  With the same seeds the gates and the five parameters are the reference's, bit for bit.  The one difference is the noise
+    field: the reference draws torch.randn(img.shape) there; the plan draws one 64-bit seed (two torch.randint words) for the in-kernel Philox
+    field instead, so from the first sample whose noise fires torch's generator stands elsewhere than the reference's (numpy's does not)."""
+    cols = {k: [None] * batch for k in ('multiply', 'additive', 'gamma', 'contrast', 'sigma', 'noise_std', 'seed')}
+    for b in range(batch):
+        if np.random.random() < p:
+            lo, hi = multiply_range
+            cols['multiply'][b] = torch.rand(size=(1, 1, 1, 1, 1)) * (hi - lo) + lo
+        if np.random.random() < p:
+            cols['additive'][b] = torch.normal(0.0, additive_std, size=(1, 1, 1, 1, 1))
+        if np.random.random() < p:
+            cols['gamma'][b] = torch.rand(1, 1) * (gamma_range[1] - gamma_range[0]) + gamma_range[0]
+        if np.random.random() < p:
+            cols['contrast'][b] = torch.rand(1, 1) * (contrast_range[1] - contrast_range[0]) + contrast_range[0]
+        if np.random.random() < p:
+            cols['sigma'][b] = torch.rand(1) * (sigma_range[1] - sigma_range[0]) + sigma_range[0]
+        if np.random.random() < p:
+            cols['noise_std'][b] = np.random.random() * noise_std_max
+            w = torch.randint(0, 1 << 32, (2,), dtype=torch.int64)
+            cols['seed'][b] = int(w[0]) | (int(w[1]) << 32)
+    return make_intensity_plan(batch, **cols)
+
+
+def _intensity_augment(img, flags, scalars, radius, taps, seeds, noise=None, workspace=None):
+    """The C ABI call.  img (B, 1, D, H, W) f32 on the device; flags / radius / seeds: B ints, scalars: B * 5 floats (multiply, additive, gamma,
+    contrast, noise std), taps: B * (2 * BLUR_MAX_RADIUS + 1) floats; noise: optional N(0, 1) tensor of img's shape that replaces the generator;
+    workspace: optional uint8 device tensor of rsuper_intensity_augment_workspace_bytes bytes (allocated here when gamma / contrast fire) -> new tensor."""
+    import ctypes
+    from ..hip import lib as _l
+    if not img.is_cuda or (noise is not None and not noise.is_cuda):
+        raise _l.RSuperHipError('intensity_augment needs device tensors (no CPU fallback)')
+    if img.dim() != 5 or img.shape[1] != 1 or img.dtype != torch.float32:
+        raise ValueError('intensity_augment: image must be float32 (B, 1, D, H, W), got %s %s' % (img.dtype, tuple(img.shape)))
+    B, _, D, H, W = img.shape
+    nt = 2 * _l.BLUR_MAX_RADIUS + 1
+    if len(flags) != B or len(radius) != B or len(seeds) != B or len(scalars) != 5 * B or len(taps) != nt * B:
+        raise ValueError('intensity_augment: per-sample records do not match the batch of %d' % B)
+    if noise is not None and (noise.dtype != torch.float32 or tuple(noise.shape) != tuple(img.shape)):
+        raise ValueError('intensity_augment: the noise tensor must be float32 of the image shape')
+    img = img.contiguous()
+    noise = None if noise is None else noise.contiguous()
+    L = _l.lib()
+    if workspace is None and any(f & 12 for f in flags):
+        workspace = torch.empty((L.rsuper_intensity_augment_workspace_bytes(B, D, H, W),), device=img.device, dtype=torch.uint8)
+    out = torch.empty_like(img)
+    with torch.cuda.device(img.device):
+        _l.check(L.rsuper_intensity_augment(
+            img.data_ptr(), out.data_ptr(), B, D, H, W, (ctypes.c_int * B)(*[int(f) for f in flags]), (ctypes.c_float * (5 * B))(*scalars),
+            (ctypes.c_int * B)(*[int(r) for r in radius]), (ctypes.c_float * (nt * B))(*taps),
+            (ctypes.c_ulonglong * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]), None if noise is None else noise.data_ptr(),
+            None if workspace is None else workspace.data_ptr(), 0 if workspace is None else workspace.numel() * workspace.element_size(),
+            torch.cuda.current_stream().cuda_stream), 'intensity_augment')
+    return out
+
+
+def intensity_launches(plan):
+    """Kernel launches intensity_augment_batch makes for this plan (0: nothing fired, the input is returned)."""
+    import ctypes
+    from ..hip import lib as _l
+    if not any(plan.flags):
+        return 0
+    return _l.lib().rsuper_intensity_augment_launches(plan.batch, (ctypes.c_int * plan.batch)(*plan.flags))
+
+
+def intensity_augment_batch(img, plan=None, noise=None, **ranges):
+    """The six intensity transforms on a batch of volumes (B, 1, D, H, W) f32 on the device, each sample with its own draws: `plan` (default:
+    plan_intensity_augment(B, **ranges), drawn here) says what fires; noise: optional explicit N(0, 1) tensor instead of the in-kernel field.
+    One dispatcher call, torch.ops.rsuper.intensity_augment; returns a new tensor -- or img itself when nothing fired in any sample."""
+    from ..hip import lib as _l
+    from ..hip import ops as _ops          # noqa: F401  (hip/ops.py pulls in hip/library.py; this order avoids the import cycle)
+    from ..hip import library as _library
+    if not img.is_cuda:                                    # the dispatcher's "no CPU kernel" error, as the project's own exception
+        raise _l.RSuperHipError('intensity_augment needs device tensors (no CPU fallback)')
+    if img.dim() != 5 or img.shape[1] != 1 or img.dtype != torch.float32:
+        raise ValueError('intensity_augment: image must be float32 (B, 1, D, H, W), got %s %s' % (img.dtype, tuple(img.shape)))
+    if plan is None:
+        plan = plan_intensity_augment(img.shape[0], **ranges)
+    elif ranges:
+        raise ValueError('intensity_augment_batch: ranges are for drawing a plan; one was given')
+    if plan.batch != img.shape[0]:
+        raise ValueError('intensity_augment_batch: the plan is for %d samples, the batch has %d' % (plan.batch, img.shape[0]))
+    if not any(plan.flags):
+        return img
+    nt = 2 * _l.BLUR_MAX_RADIUS + 1
+    scalars, taps = [], []
+    for b in range(plan.batch):
+        scalars += [plan.multiply[b], plan.additive[b], plan.gamma[b], plan.contrast[b], plan.noise_std[b]]
+        taps += (list(plan.taps[b]) + [0.0] * nt)[:nt]    # a radius above the limit is refused by the call itself, never clamped
+    seeds = [s - (1 << 64) if s >= (1 << 63) else s for s in plan.seed]        # the schema's ints are signed 64-bit
+    return _library.install_intensity_ops(_intensity_augment)(img, list(plan.flags), scalars, list(plan.radius), taps, seeds, noise, None)
