@@ -589,6 +589,38 @@ int rsuper_intensity_augment(const float* img, float* out, int B, int D, int H, 
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Whole-CT preprocessing and spacing resampling -- predict_abdomenatlas.py preprocess :325-356 (from the clip onward), pad_to_training_size
+ * :249-306, unpad_img :311-322, resample_image_with_gpu :718-742.
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_VOX_U8 0
+#define RSUPER_VOX_F32 1
+#define RSUPER_VOX_I16 2
+#define RSUPER_RESAMPLE_NEAREST 0
+#define RSUPER_RESAMPLE_TRILINEAR 1
+/* z-score of clip(x, lo, hi) in two launches.  x: device [D][H][W], dtype RSUPER_VOX_I16 (HU as a CT stores them) or RSUPER_VOX_F32, D * H * W < 2^31.
+ * rsuper_ct_stats writes a fixed number of per-block f64 partials (count, sum, sum of squares) into `workspace` (device, 8-byte aligned, at least
+ * rsuper_ct_stats_workspace_bytes() bytes; every partial is written: no memset).  rsuper_ct_normalize re-reduces them in a fixed order in every block,
+ * forms mean and the unbiased std in f64, rounds each to f32, stores them to mean_std[0..1] (device) and writes (clip(x) - mean) / std (IEEE
+ * division) into out [Do][Ho][Wo] f32 at the box (z_lo, y_lo, x_lo) + (D, H, W); every voxel outside the box is 0 (the reference pads after
+ * normalising).  No atomics, no host synchronisation between the two launches, bit-reproducible.  Nothing degenerate is special-cased: a constant
+ * volume gives 0 / 0 = NaN inside the box, D * H * W == 1 gives NaN.  rsuper_pad_box: the same padded write of x itself (no clip, no statistics).
+ * Null pointers, non-positive sizes, a box outside the output, out == x or a short workspace -> RSUPER_ERR_ARG, checked before anything is launched. */
+long rsuper_ct_stats_workspace_bytes(void);
+int rsuper_ct_stats(const void* x, int dtype, int D, int H, int W, float lo, float hi, void* workspace, long workspace_bytes, void* stream);
+int rsuper_ct_normalize(const void* x, int dtype, int D, int H, int W, float lo, float hi, const void* workspace, long workspace_bytes, float* out,
+                        int Do, int Ho, int Wo, int z_lo, int y_lo, int x_lo, float* mean_std, void* stream);
+int rsuper_pad_box(const void* x, int dtype, int D, int H, int W, float* out, int Do, int Ho, int Wo, int z_lo, int y_lo, int x_lo, void* stream);
+/* One launch: src [C][Dp][Hp][Wp] (RSUPER_VOX_U8 / RSUPER_VOX_F32), of every plane the sub-box (z0, y0, x0) + (D, H, W) -> out [C][Do][Ho][Wo].
+ * mode RSUPER_RESAMPLE_NEAREST: scale = (float)n_in / (float)n_out, src = min((int)floorf((float)dst * scale), n_in - 1) (F.interpolate 'nearest');
+ * RSUPER_RESAMPLE_TRILINEAR: scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0, s = scale * (float)dst, i0 = min((int)s, n_in - 1),
+ * i1 = i0 + (i0 < n_in - 1), l1 = s - (float)i0, l0 = 1 - l1 (align_corners = True), lerps in x, y, z order, all f32.  out_dtype RSUPER_VOX_F32: the
+ * value; RSUPER_VOX_U8 with use_threshold: value > threshold as 0 / 1; RSUPER_VOX_U8 without: u8 input and nearest only (a copy of bytes), anything
+ * else -> RSUPER_ERR_UNSUPPORTED.  Dp * Hp * Wp and Do * Ho * Wo < 2^31, C <= 65535.  Null pointers, non-positive sizes, a sub-box outside the
+ * tensor, an unknown dtype or mode -> RSUPER_ERR_ARG, checked before anything is launched. */
+int rsuper_resample3d(const void* src, int in_dtype, int C, int Dp, int Hp, int Wp, int z0, int y0, int x0, int D, int H, int W, void* out,
+                      int out_dtype, int Do, int Ho, int Wo, int mode, int use_threshold, float threshold, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser -- train_ddp.py:352-357, training/utils.py:46-51,154-161.  host_* are HOST arrays of device pointers.
  * ------------------------------------------------------------------------------------------------ */
 /* *total_sq = sum of squared elements of the n gradient tensors (f64, deterministic order).  The accumulator need not be zeroed: the first launch

@@ -138,6 +138,11 @@ _SIGS = {
     'rsuper_edt3_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_edt3': (c_int, [P] + [c_int] * 9 + [c_double] * 3 + [P, P, c_long, P]),
     'rsuper_surfel_gather': (c_int, [P] + [c_int] * 9 + [P, P, P, P, P, c_long, P]),
+    'rsuper_ct_stats_workspace_bytes': (c_long, []),
+    'rsuper_ct_stats': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_long, P]),
+    'rsuper_ct_normalize': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_long, P] + [c_int] * 6 + [P, P]),
+    'rsuper_pad_box': (c_int, [P, c_int, c_int, c_int, c_int, P] + [c_int] * 6 + [P]),
+    'rsuper_resample3d': (c_int, [P, c_int] + [c_int] * 10 + [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

@@ -24,6 +24,9 @@ intensity augmentation of the loader (training/augmentation.py; no derivative):
 validation metrics (metric/metrics.py; no derivative):
     torch.ops.rsuper.surface_distances(mask_gt, mask_pred, spacing, area_table) -> (sorted distances and areas per plane, counts)
     torch.ops.rsuper.edt3(codes, box, spacing, workspace) -> squared distances
+whole-case preprocessing and resampling (inference/preprocess.py, inference/resample.py; no derivative):
+    torch.ops.rsuper.ct_normalize(hu, lo, hi, out_shape, offset, workspace) -> (z-scored, zero-padded volume, (mean, std))
+    torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -199,6 +202,31 @@ def install_intensity_ops(intensity_augment):
         _INTENSITY_OP = _register_plain('intensity_augment', '(Tensor img, int[] flags, float[] scalars, int[] radius, float[] taps, int[] seeds, '
                                         'Tensor? noise=None, Tensor? workspace=None) -> Tensor', intensity_augment)
     return _INTENSITY_OP
+
+
+_PREPROCESS_OP = None
+
+
+def install_preprocess_ops(ct_normalize):
+    """Register the whole-CT z-score of inference/preprocess.py (at the end of that module; idempotent) as a plain CUDA kernel: the network's input
+    has no derivative."""
+    global _PREPROCESS_OP
+    if _PREPROCESS_OP is None:
+        _PREPROCESS_OP = _register_plain('ct_normalize', '(Tensor hu, float lo, float hi, int[] out_shape, int[] offset, Tensor? workspace=None) '
+                                         '-> (Tensor, Tensor)', ct_normalize)
+    return _PREPROCESS_OP
+
+
+_RESAMPLE_OP = None
+
+
+def install_resample_ops(resample3d):
+    """Register the class-stack resampler of inference/resample.py (at the end of that module; idempotent) as a plain CUDA kernel: labels and
+    thresholded probabilities have no derivative."""
+    global _RESAMPLE_OP
+    if _RESAMPLE_OP is None:
+        _RESAMPLE_OP = _register_plain('resample3d', '(Tensor x, int[] box, int[] out_size, str interp, float? threshold=None) -> Tensor', resample3d)
+    return _RESAMPLE_OP
 
 
 _METRIC_OPS = None
