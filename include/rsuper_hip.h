@@ -621,6 +621,37 @@ int rsuper_resample3d(const void* src, int in_dtype, int C, int Dp, int Hp, int 
                       int out_dtype, int Do, int Ho, int Wo, int mode, int use_threshold, float threshold, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Crop-on-tumour from a whole CT with a bit-packed label -- training/augmentation.py random_crop_on_tumor :600, negative_crop :662, organ_crop :675,
+ * tumor_crop :716, crop_around_coordinate_3d :498, pad_volume_pair :1023.
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_CROP_CHUNK 16384
+#define RSUPER_CROP_MAX_CLASSES 64
+/* packed: device [B][P][D][H][W] u8 as np.packbits(axis = class) wrote it (class c = bit 7 - (c & 7) of byte plane c >> 3), ceil(C / 8) <= P <= 8,
+ * C <= RSUPER_CROP_MAX_CLASSES, D * H * W < 2^31.  Launch 1 writes the chunk table [B][chunks][C + 1] int32 into `workspace` (device, 4-byte aligned,
+ * rsuper_class_counts_workspace_bytes bytes; chunks = ceil(D * H * W / RSUPER_CROP_CHUNK), a chunk = RSUPER_CROP_CHUNK consecutive voxels in row-major
+ * order): per chunk the set voxels of every class and, in column C, the voxels whose P bytes are all zero (the background).  Launch 2 sums the rows
+ * into totals [B][C + 1] int64 (device).  Every entry is written: no memset, no atomics, bit-reproducible.  Any base alignment and any voxel count.
+ * plain != 0: the label is [B][C][D][H][W] bytes instead (P == C, class c = plane c, set = byte not zero), the table is the same. */
+long rsuper_class_counts_workspace_bytes(int B, int C, int D, int H, int W);
+int rsuper_class_counts(const uint8_t* packed, int B, int P, int C, int plain, int D, int H, int W, void* workspace, long workspace_bytes, long long* totals,
+                        void* stream);
+/* zyx (device, 3 int32) = (z + add_z, y + add_y, x + add_x) of the k-th voxel, in row-major order, of sample b whose bit of class `column` is set
+ * (column == C: whose P bytes are all zero): torch.nonzero(mask)[k].  workspace: the chunk table rsuper_class_counts wrote for this tensor.  count:
+ * the column's total as the caller read it; k < 0 or k >= count -> RSUPER_ERR_ARG, nothing is launched.  One block; it reads the table and one chunk. */
+int rsuper_select_voxel(const uint8_t* packed, int B, int P, int C, int plain, int D, int H, int W, const void* workspace, long workspace_bytes, int b, int column,
+                        long k, long count, int add_z, int add_y, int add_x, int* zyx, void* stream);
+/* One launch per 8 samples: img [B][Ci][D][H][W] (RSUPER_VOX_F32 or RSUPER_VOX_I16; Ci == 0: no image) -> img_out [B][Ci][d][h][w] f32, and nvol <=
+ * RSUPER_AFFINE_MAX_VOLUMES byte volumes vols[k] [B][planes[k]][D][H][W] -> vols_out[k] [B][planes[k]][d][h][w] (vols, vols_out, planes: HOST arrays).
+ * The source counts as zero-padded to (max(D, pad_d), max(H, pad_h), max(W, pad_w)) with (padded - real) / 2 voxels on the low side (pad_volume_pair);
+ * all coordinates are padded coordinates and no padded copy is made.  origin: HOST [B][3] ints.  center == NULL: the crop's corner itself, inside
+ * [0, padded size - crop].  center: device [B][3] int32 (rsuper_select_voxel's output): corner = clip(center - crop / 2 + origin, 0, padded size -
+ * crop), origin being the host-drawn shift (crop_around_coordinate_3d 'small_rnd_shift').  origin_out: optional device [B][3] int32 that receives the
+ * corner used.  A crop larger than the padded source, a corner outside it or null pointers -> RSUPER_ERR_ARG, checked before anything is launched. */
+int rsuper_crop_box(const void* img, int img_dtype, float* img_out, int B, int Ci, int D, int H, int W, int nvol, const uint8_t* const* vols,
+                    uint8_t* const* vols_out, const int* planes, int d, int h, int w, int pad_d, int pad_h, int pad_w, const int* center,
+                    const int* origin, int* origin_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser -- train_ddp.py:352-357, training/utils.py:46-51,154-161.  host_* are HOST arrays of device pointers.
  * ------------------------------------------------------------------------------------------------ */
 /* *total_sq = sum of squared elements of the n gradient tensors (f64, deterministic order).  The accumulator need not be zeroed: the first launch

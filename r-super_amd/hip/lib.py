@@ -143,6 +143,10 @@ _SIGS = {
     'rsuper_ct_normalize': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_long, P] + [c_int] * 6 + [P, P]),
     'rsuper_pad_box': (c_int, [P, c_int, c_int, c_int, c_int, P] + [c_int] * 6 + [P]),
     'rsuper_resample3d': (c_int, [P, c_int] + [c_int] * 10 + [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    'rsuper_class_counts_workspace_bytes': (c_long, [c_int] * 5),
+    'rsuper_class_counts': (c_int, [P] + [c_int] * 7 + [P, c_long, P, P]),
+    'rsuper_select_voxel': (c_int, [P] + [c_int] * 7 + [P, c_long, c_int, c_int, c_long, c_long, c_int, c_int, c_int, P, P]),
+    'rsuper_crop_box': (c_int, [P, c_int, P] + [c_int] * 6 + [P, P, P] + [c_int] * 6 + [P, P, P, P]),
     'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

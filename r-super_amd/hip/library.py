@@ -24,6 +24,10 @@ intensity augmentation of the loader (training/augmentation.py; no derivative):
 validation metrics (metric/metrics.py; no derivative):
     torch.ops.rsuper.surface_distances(mask_gt, mask_pred, spacing, area_table) -> (sorted distances and areas per plane, counts)
     torch.ops.rsuper.edt3(codes, box, spacing, workspace) -> squared distances
+crop-on-tumour from a whole CT (training/augmentation.py; no derivative):
+    torch.ops.rsuper.class_counts(packed, C, plain, workspace) -> (totals, chunk table)
+    torch.ops.rsuper.select_voxel(packed, C, plain, table, b, column, k, count, add) -> (z, y, x)
+    torch.ops.rsuper.crop_box(img, volumes, size, pad, center, origin) -> (image crop, volume crops, corners)
 whole-case preprocessing and resampling (inference/preprocess.py, inference/resample.py; no derivative):
     torch.ops.rsuper.ct_normalize(hu, lo, hi, out_shape, offset, workspace) -> (z-scored, zero-padded volume, (mean, std))
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
@@ -189,6 +193,24 @@ def install_augment_ops(affine_crop):
         _AUG_OP = _register_plain('affine_crop', '(Tensor img, Tensor[] volumes, Tensor theta, int[] out_size, int[] offsets) -> (Tensor, Tensor[])',
                                   affine_crop)
     return _AUG_OP
+
+
+_CROP_OPS = None
+
+
+def install_crop_ops(class_counts, select_voxel, crop_box):
+    """Register the crop-on-tumour operators of training/augmentation.py (on their first use; idempotent) as plain CUDA kernels: counts, a voxel
+    index and a copied box have no derivative."""
+    global _CROP_OPS
+    if _CROP_OPS is None:
+        _CROP_OPS = (
+            _register_plain('class_counts', '(Tensor packed, int C, bool plain, Tensor? workspace=None) -> (Tensor, Tensor)', class_counts),
+            _register_plain('select_voxel', '(Tensor packed, int C, bool plain, Tensor table, int b, int column, int k, int count, int[] add) -> Tensor',
+                            select_voxel),
+            _register_plain('crop_box', '(Tensor? img, Tensor[] volumes, int[] size, int[] pad, Tensor? center, int[] origin) -> (Tensor, Tensor[], Tensor)',
+                            crop_box),
+        )
+    return _CROP_OPS
 
 
 _INTENSITY_OP = None

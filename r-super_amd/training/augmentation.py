@@ -435,3 +435,372 @@ def intensity_augment_batch(img, plan=None, noise=None, **ranges):
         taps += (list(plan.taps[b]) + [0.0] * nt)[:nt]    # a radius above the limit is refused by the call itself, never clamped
     seeds = [s - (1 << 64) if s >= (1 << 63) else s for s in plan.seed]        # the schema's ints are signed 64-bit
     return _library.install_intensity_ops(_intensity_augment)(img, list(plan.flags), scalars, list(plan.radius), taps, seeds, noise, None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Crop-on-tumour on the device (csrc/crop.hip): random_crop_on_tumor (augmentation.py:600), negative_crop (:662), organ_crop (:675),
+# tumor_crop (:716), crop_around_coordinate_3d (:498) and pad_volume_pair (:1023) for a whole CT whose label is a PackedBits (or a plain
+# u8 / int64 (1, C, D, H, W) label).  The label is never inflated: rsuper_class_counts popcounts the packed bytes into a chunk table and
+# (C + 1) totals, the draws are made on the host from the totals (plan_crop_on_tumor, the one device-to-host read of a sample),
+# rsuper_select_voxel finds "the k-th set voxel in row-major order" = torch.nonzero(mask)[k] on the device, and rsuper_crop_box cuts the
+# image and the byte planes around it.  The chosen voxel and the crop's corner stay on the device.  Every function takes `pad=(pd, ph, pw)`
+# in addition to the reference's arguments: the source then counts as pad_volume_pair(img, lab, pd, ph, pw) would have padded it, without
+# the padded copy being made.  No CPU kernel: a CPU tensor raises RSuperHipError.
+# ---------------------------------------------------------------------------------------------------------------------------
+CROP_CHUNK = 16384         # RSUPER_CROP_CHUNK of the header: voxels per row of the chunk table
+VOX_F32, VOX_I16 = 1, 2    # RSUPER_VOX_* of the header
+
+
+def padded_size(size, pad):
+    """(padded extents, padding on the low side) of pad_volume_pair (:1049-1066): max(size, desired), (padded - size) // 2."""
+    size = [int(s) for s in size]
+    if pad is None:
+        return size, [0, 0, 0]
+    full = [max(s, int(p)) for s, p in zip(size, pad)]
+    return full, [(f - s) // 2 for f, s in zip(full, size)]
+
+
+class CropPlan:
+    """What the draws of one crop decided.  branch: 'tumor' / 'background' / 'organ' (the function entered); fallback: it fell back to crop_3d's random
+    corner `origin`; otherwise the crop is centred on voxel number `rank` (row-major) of `column` (a class, or C = the background column) whose total
+    is `count`, shifted by `offsets`; crop_organ: what the reference returns with return_crop_organ (a class index or 'random')."""
+
+    def __init__(self, branch):
+        self.branch, self.fallback, self.column, self.rank, self.count = branch, False, None, None, None
+        self.offsets, self.origin, self.crop_organ = None, None, 'random'
+
+    def __repr__(self):
+        return 'CropPlan(%s)' % ', '.join('%s=%r' % kv for kv in sorted(vars(self).items()))
+
+
+def _draw_center(plan, column, count, crop):
+    """center = voxels[torch.randint(0, len(voxels), (1,))][0], then the three shifts of 'small_rnd_shift' (:530-537)."""
+    plan.column, plan.count = int(column), int(count)
+    plan.rank = int(torch.randint(0, int(count), (1,)))
+    plan.offsets = [int(np.random.randint(-int(c * 0.5), int(c * 0.5) + 1)) for c in crop]
+    return plan
+
+
+def _fall_back(plan, size, crop):
+    plan.fallback, plan.origin, plan.crop_organ = True, crop_offsets(size, crop, 'random'), 'random'
+    return plan
+
+
+def plan_tumor_crop(totals, lesion_classes, size, crop):
+    """tumor_crop's draws (:716-738) from the (C + 1) totals: no lesion voxel -> crop_3d's three draws; otherwise torch.randint over the lesion classes
+    that are present, torch.randint over the chosen class's voxels, the three shifts."""
+    plan = CropPlan('tumor')
+    lesion_classes = [int(c) for c in lesion_classes]
+    possibilities = [i for i, c in enumerate(lesion_classes) if totals[c] > 0]
+    if not possibilities:
+        return _fall_back(plan, size, crop)
+    chosen = possibilities[torch.randint(0, len(possibilities), (1,)).item()]
+    plan.crop_organ = lesion_classes[chosen]
+    return _draw_center(plan, lesion_classes[chosen], totals[lesion_classes[chosen]], crop)
+
+
+def plan_organ_crop(totals, lesion_classes, size, crop, foreground_classes=None):
+    """organ_crop's draws (:675-710): the non-lesion classes (of foreground_classes when given) that are present, one by torch.randint, then a voxel."""
+    plan = CropPlan('organ')
+    C = len(totals) - 1
+    clss = [c for c in range(C) if c not in lesion_classes and (foreground_classes is None or c in foreground_classes) and totals[c] > 0]
+    if not clss:
+        return _fall_back(plan, size, crop)
+    plan.crop_organ = clss[torch.randint(0, len(clss), (1,)).item()]
+    return _draw_center(plan, plan.crop_organ, totals[plan.crop_organ], crop)
+
+
+def plan_negative_crop(totals, size, crop):
+    """negative_crop's draws (:662-672): a voxel of the background column (label.sum(0) == 0), or crop_3d's when there is none."""
+    plan = CropPlan('background')
+    C = len(totals) - 1
+    if totals[C] == 0:
+        return _fall_back(plan, size, crop)
+    return _draw_center(plan, C, totals[C], crop)
+
+
+def plan_crop_on_tumor(totals, lesion_classes, size, crop, tumor_case, tumor_prob=None, foreground_prob=None, background_prob=None,
+                       foreground_classes=None):
+    """The draws of random_crop_on_tumor (:618-652) in the reference's order: np.random.random() picks the branch, then that branch's draws.
+    totals: the (C + 1) voxel counts of the (padded) volume -- classes 0 .. C - 1, then the background; size: its (padded) extents; crop: (d, h, w)."""
+    totals = [int(t) for t in totals]
+    rnd = np.random.random()
+    if (tumor_prob is None) or (foreground_prob is None) or (background_prob is None):
+        tumor_prob, foreground_prob, background_prob = (0.9, 0.05, 0.05) if tumor_case else (0, 0.9, 0.1)
+    if rnd < tumor_prob:
+        return plan_tumor_crop(totals, lesion_classes, size, crop)
+    if rnd < (tumor_prob + background_prob):
+        return plan_negative_crop(totals, size, crop)
+    return plan_organ_crop(totals, lesion_classes, size, crop, foreground_classes)
+
+
+def _crop_ops():
+    from ..hip import ops as _ops          # noqa: F401  (hip/ops.py pulls in hip/library.py; this order avoids the import cycle)
+    from ..hip import library as _library
+    return _library.install_crop_ops(_class_counts, _select_voxel, _crop_box)
+
+
+def _need_device(what, *ts):
+    from ..hip import lib as _l
+    if any(t is not None and not t.is_cuda for t in ts):
+        raise _l.RSuperHipError('%s needs device tensors (no CPU fallback)' % what)
+
+
+def _class_counts(packed, C, plain, workspace=None):
+    """The C ABI call.  packed (B, P, D, H, W) u8 -> (totals (B, C + 1) int64, the chunk table as the uint8 workspace it lives in)."""
+    from ..hip import lib as _l
+    _need_device('class_counts', packed)
+    if packed.dim() != 5 or packed.dtype != torch.uint8:
+        raise ValueError('class_counts: the label must be uint8 (B, P, D, H, W), got %s %s' % (packed.dtype, tuple(packed.shape)))
+    if not packed.is_contiguous():
+        raise ValueError('class_counts: the label must be contiguous')
+    B, P, D, H, W = packed.shape
+    L = _l.lib()
+    need = L.rsuper_class_counts_workspace_bytes(B, int(C), D, H, W)
+    if workspace is None:
+        workspace = torch.empty((need,), device=packed.device, dtype=torch.uint8)
+    totals = torch.empty((B, int(C) + 1), device=packed.device, dtype=torch.int64)
+    with torch.cuda.device(packed.device):
+        _l.check(L.rsuper_class_counts(packed.data_ptr(), B, P, int(C), int(bool(plain)), D, H, W, workspace.data_ptr(),
+                                       workspace.numel() * workspace.element_size(), totals.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                 'class_counts')
+    return totals, workspace
+
+
+def _select_voxel(packed, C, plain, table, b, column, k, count, add):
+    """The C ABI call -> (3,) int32 device tensor (z, y, x) + add.  k outside [0, count) is refused before anything is launched."""
+    from ..hip import lib as _l
+    _need_device('select_voxel', packed, table)
+    B, P, D, H, W = packed.shape
+    out = torch.empty((3,), device=packed.device, dtype=torch.int32)
+    with torch.cuda.device(packed.device):
+        _l.check(_l.lib().rsuper_select_voxel(packed.data_ptr(), B, P, int(C), int(bool(plain)), D, H, W, table.data_ptr(),
+                                              table.numel() * table.element_size(), int(b), int(column), int(k), int(count),
+                                              int(add[0]), int(add[1]), int(add[2]), out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                 'select_voxel')
+    return out
+
+
+def _crop_box(img, volumes, size, pad, center, origin):
+    """The C ABI call.  img (B, Ci, D, H, W) f32 / int16 or None, volumes: list of (B, P, D, H, W) u8, size (d, h, w), pad (pd, ph, pw) (0 = none),
+    center: None or (B, 3) int32 device tensor, origin: B * 3 ints (the corner, or with a center the shift) -> (f32 image crop, volume crops,
+    (B, 3) int32 device tensor of the corners used)."""
+    import ctypes
+    from ..hip import lib as _l
+    _need_device('crop_box', img, center, *volumes)
+    ref = img if img is not None else volumes[0]
+    if ref.dim() != 5:
+        raise ValueError('crop_box: expected (B, C, D, H, W) tensors')
+    B, _, D, H, W = ref.shape
+    if img is not None and img.dtype not in (torch.float32, torch.int16):
+        raise ValueError('crop_box: the image must be float32 or int16, got %s' % img.dtype)
+    for v in volumes:
+        if v.dtype != torch.uint8 or v.dim() != 5 or v.shape[0] != B or tuple(v.shape[2:]) != (D, H, W):
+            raise ValueError('crop_box: byte volumes must be uint8 (B, P, D, H, W) on the image grid')
+    d, h, w = (int(s) for s in size)
+    pad = [int(p) for p in pad]
+    origin = [int(o) for o in origin]
+    if len(origin) != 3 * B or len(pad) != 3:
+        raise ValueError('crop_box: one (z, y, x) triple per sample and one pad triple')
+    if center is not None and (center.dtype != torch.int32 or center.numel() != 3 * B):
+        raise ValueError('crop_box: the centre must be a (B, 3) int32 tensor')
+    img = None if img is None else img.contiguous()
+    volumes = [v.contiguous() for v in volumes]
+    center = None if center is None else center.contiguous()
+    Ci = 0 if img is None else img.shape[1]
+    out = torch.empty((B, Ci, d, h, w), device=ref.device, dtype=torch.float32)
+    outs = [torch.empty((B, v.shape[1], d, h, w), device=ref.device, dtype=torch.uint8) for v in volumes]
+    used = torch.empty((B, 3), device=ref.device, dtype=torch.int32)
+    n = len(volumes)
+    src = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in volumes])
+    dst = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in outs])
+    planes = (ctypes.c_int * max(n, 1))(*[v.shape[1] for v in volumes])
+    with torch.cuda.device(ref.device):
+        _l.check(_l.lib().rsuper_crop_box(None if img is None else img.data_ptr(), VOX_I16 if (img is not None and img.dtype == torch.int16) else VOX_F32,
+                                          out.data_ptr() if Ci else None, B, Ci, D, H, W, n, src, dst, planes, d, h, w, pad[0], pad[1], pad[2],
+                                          None if center is None else center.data_ptr(), (ctypes.c_int * (3 * B))(*origin), used.data_ptr(),
+                                          torch.cuda.current_stream().cuda_stream), 'crop_box')
+    return out, outs, used
+
+
+class LabelCounts:
+    """The chunk table and the (B, C + 1) totals of one label, as rsuper_class_counts left them on the device.  `host(b)` is the one device-to-host read."""
+
+    def __init__(self, planes, C, plain, totals, table):
+        self.planes, self.C, self.plain, self.totals, self.table = planes, int(C), bool(plain), totals, table
+        self._host = None
+
+    def host(self, b=0):
+        if self._host is None:
+            self._host = self.totals.cpu().tolist()
+        return list(self._host[b])
+
+
+def _label_planes(lab, what):
+    """PackedBits -> (its packed bytes, C, False); a plain int64 / u8 / bool (B, C, D, H, W) label -> (u8 planes, C, True)."""
+    if hasattr(lab, 'packed'):
+        return lab.packed, lab.C, False
+    _need_device(what, lab)
+    if lab.dim() != 5:
+        raise ValueError('%s: the label must be (B, C, D, H, W)' % what)
+    return _as_bytes(lab, what).contiguous(), lab.shape[1], True
+
+
+def _label_like(lab, t):
+    if hasattr(lab, 'packed'):
+        return type(lab)(t, lab.C)
+    return t.to(lab.dtype)
+
+
+def class_counts(lab):
+    """Voxel counts of every class and of the background of a PackedBits or plain label on the device -> LabelCounts (torch.ops.rsuper.class_counts)."""
+    planes, C, plain = _label_planes(lab, 'class_counts')
+    totals, table = _crop_ops()[0](planes, C, plain, None)
+    return LabelCounts(planes, C, plain, totals, table)
+
+
+def select_voxel(counts, column, k, count=None, b=0, add=(0, 0, 0)):
+    """(z, y, x) + add of the k-th voxel (row-major) of `column` (a class, or counts.C = the background) of sample b, as a (3,) int32 device tensor:
+    torch.nonzero(mask)[k] without the mask (torch.ops.rsuper.select_voxel).  count: the column's total when the caller has already read it (default:
+    read here).  k outside [0, count) raises RSuperHipError."""
+    if count is None:
+        count = counts.host(b)[column]
+    return _crop_ops()[1](counts.planes, counts.C, counts.plain, counts.table, int(b), int(column), int(k), int(count), [int(v) for v in add])
+
+
+def crop_box(img, volumes, size, pad=None, origin=None, center=None, offset=None):
+    """Box crops of size (d, h, w) of img (B, Ci, D, H, W) f32 / int16 (or None) and of the byte volumes (packed u8 tensors or PackedBits), the source
+    zero-padded to `pad` as pad_volume_pair pads, in padded coordinates (torch.ops.rsuper.crop_box).  Either origin = B * 3 ints (the corners), or
+    center = (B, 3) int32 device tensor and offset = B * 3 ints: corner = clip(center - size // 2 + offset, 0, padded size - size).
+    -> (f32 image crop or None, tuple of crops of the kinds given, (B, 3) int32 device tensor of the corners used)."""
+    if (origin is None) == (center is None):
+        raise ValueError('crop_box: give either origin or center (+ offset)')
+    ref = img if img is not None else _packed_of(volumes[0])
+    B = ref.shape[0]
+    shift = list(origin) if center is None else list(offset if offset is not None else [0, 0, 0] * B)
+    out, outs, used = _crop_ops()[2](img, [_packed_of(v) for v in volumes], [int(s) for s in size], [0, 0, 0] if pad is None else [int(p) for p in pad],
+                                     None if center is None else center.reshape(B, 3), [int(s) for s in shift])
+    return (out if img is not None else None), tuple(_like(v, t) for v, t in zip(volumes, outs)), used
+
+
+def pad_volume_pair(input_tensor, label_tensor, desired_d, desired_h, desired_w):
+    """pad_volume_pair (:1023-1075) on the device: zeros on both sides, pad // 2 on the low side; tensors that need no padding are returned as they
+    are.  One crop_box launch whose crop is the whole padded volume (the image comes back as float32).  The crop functions below do not need it: they
+    take pad= and never make this copy."""
+    size = tuple(input_tensor.shape[-3:])
+    if size != tuple(label_tensor.shape[-3:]):
+        raise ValueError('The input and label tensors must have the same spatial dimensions.')
+    full, _ = padded_size(size, (desired_d, desired_h, desired_w))
+    if list(size) == full:
+        return input_tensor, label_tensor
+    planes, _, _ = _label_planes(label_tensor, 'pad_volume_pair')
+    img, (lab,), _ = crop_box(input_tensor, (planes,), full, pad=full, origin=[0, 0, 0] * input_tensor.shape[0])
+    return img, _label_like(label_tensor, lab)
+
+
+def crop_planned(tensor_img, tensor_lab, plan_fn, crop, pad=None, counts=None, foreground=None):
+    """The chain behind every crop function: class_counts -> one read of the totals -> plan_fn(totals, padded size) draws a CropPlan ->
+    select_voxel -> crop_box.  With pad= the totals are those of the padded volume (its padding is background).  A background voxel of a padded
+    volume is ranked in the padded volume's row-major order, which no table of the real volume gives: for that branch alone the padded label (not
+    the image) is written once and counted again.  -> (image crop, label crop of tensor_lab's kind [, foreground crop], plan, corner (1, 3) int32)."""
+    _need_device('crop_on_tumor', tensor_img)
+    if tensor_img.dim() != 5 or tensor_img.shape[0] != 1:
+        raise ValueError('expected a (1, C, D, H, W) volume, got %s' % (tuple(tensor_img.shape),))
+    planes, C, plain = _label_planes(tensor_lab, 'crop_on_tumor')
+    assert planes.shape[0] == 1
+    size = tuple(tensor_img.shape[2:])
+    if tuple(planes.shape[2:]) != size:
+        raise ValueError('The input and label tensors must have the same spatial dimensions.')
+    crop = [int(c) for c in crop]
+    full, lo = padded_size(size, pad)
+    if any(c > f for c, f in zip(crop, full)):
+        raise ValueError('crop %s is larger than the (padded) volume %s' % (crop, full))
+    if counts is None:
+        counts = class_counts(tensor_lab)
+    totals = counts.host(0)
+    extra = full[0] * full[1] * full[2] - size[0] * size[1] * size[2]
+    totals[C] += extra
+    plan = plan_fn(totals, full)
+    vols = [planes]
+    if foreground is not None:
+        fg = _as_bytes(foreground, 'foreground')
+        vols.append(fg.reshape((1,) * (5 - fg.ndim) + tuple(fg.shape)))
+    if plan.fallback:
+        out, outs, used = crop_box(tensor_img, vols, crop, pad=full, origin=plan.origin)
+    else:
+        if plan.column == C and extra:
+            padded = crop_box(None, (planes,), full, pad=full, origin=[0, 0, 0])[1][0]
+            pc = _crop_ops()[0](padded, C, plain, None)
+            center = _crop_ops()[1](padded, C, plain, pc[1], 0, C, plan.rank, plan.count, [0, 0, 0])
+        else:
+            center = select_voxel(counts, plan.column, plan.rank, plan.count, add=lo)
+        out, outs, used = crop_box(tensor_img, vols, crop, pad=full, center=center, offset=plan.offsets)
+    res = (out, _label_like(tensor_lab, outs[0]))
+    if foreground is not None:
+        res += (outs[1].to(foreground.dtype),)
+    return res + (plan, used)
+
+
+def _organ_name(plan, class_names):
+    co = plan.crop_organ
+    return class_names[co] if (co is not None and co != 'random' and class_names is not None) else co
+
+
+def random_crop_on_tumor(tensor_img, tensor_lab, lesion_classes, d, h, w, tumor_case, tumor_prob=None, foreground_prob=None, background_prob=None,
+                         return_crop_organ=False, class_names=None, foreground_classes=None, pad=None, counts=None):
+    """random_crop_on_tumor (:600-660) on a device image (1, Ci, D, H, W) f32 / int16 and a PackedBits or plain (1, C, D, H, W) label."""
+    r = crop_planned(tensor_img, tensor_lab, lambda t, s: plan_crop_on_tumor(t, lesion_classes, s, [d, h, w], tumor_case, tumor_prob, foreground_prob,
+                                                                            background_prob, foreground_classes), [d, h, w], pad, counts)
+    return (r[0], r[1], _organ_name(r[2], class_names)) if return_crop_organ else r[:2]
+
+
+def negative_crop(tensor_img, tensor_lab, lesion_classes, d, h, w, pad=None, counts=None):
+    """negative_crop (:662-673): around a random background voxel, or crop_3d's random crop when every voxel carries a label."""
+    return crop_planned(tensor_img, tensor_lab, lambda t, s: plan_negative_crop(t, s, [d, h, w]), [d, h, w], pad, counts)[:2]
+
+
+def organ_crop(tensor_img, tensor_lab, lesion_classes, d, h, w, return_crop_organ=False, foreground_classes=None, pad=None, counts=None):
+    """organ_crop (:675-714): around a random voxel of a random non-lesion class that is present."""
+    r = crop_planned(tensor_img, tensor_lab, lambda t, s: plan_organ_crop(t, lesion_classes, s, [d, h, w], foreground_classes), [d, h, w], pad, counts)
+    return (r[0], r[1], r[2].crop_organ) if return_crop_organ else r[:2]
+
+
+def tumor_crop(tensor_img, tensor_lab, lesion_classes, d, h, w, return_crop_organ=False, pad=None, counts=None):
+    """tumor_crop (:716-742): around a random voxel of a random lesion class that is present."""
+    r = crop_planned(tensor_img, tensor_lab, lambda t, s: plan_tumor_crop(t, lesion_classes, s, [d, h, w]), [d, h, w], pad, counts)
+    return (r[0], r[1], r[2].crop_organ) if return_crop_organ else r[:2]
+
+
+def crop_around_coordinate_3d(tensor_img, tensor_lab, crop_size, coordinate, mode, foreground=None, pad=None):
+    """crop_around_coordinate_3d (:498-559).  coordinate: three ints, or for 'small_rnd_shift' a (3,) int32 device tensor (select_voxel's output), which
+    is then never read by the host.  'random' and 'center' compute their corner on the host, so a device coordinate is read once for them."""
+    assert mode in ['random', 'center', 'small_rnd_shift'], "Invalid Mode, should be 'random' or 'center'"
+    if isinstance(crop_size, int):
+        crop_size = [crop_size] * 3
+    crop_size = [int(c) for c in crop_size]
+    _need_device('crop_around_coordinate_3d', tensor_img)
+    planes, _, _ = _label_planes(tensor_lab, 'crop_around_coordinate_3d')
+    full, _ = padded_size(tensor_img.shape[2:], pad)
+    if any(c > f for c, f in zip(crop_size, full)):
+        raise ValueError('crop %s is larger than the (padded) volume %s' % (crop_size, full))
+    vols = [planes]
+    if foreground is not None:
+        fg = _as_bytes(foreground, 'foreground')
+        vols.append(fg.reshape((1,) * (5 - fg.ndim) + tuple(fg.shape)))
+    on_device = isinstance(coordinate, torch.Tensor) and coordinate.is_cuda
+    if mode == 'small_rnd_shift':
+        offs = [int(np.random.randint(-int(c * 0.5), int(c * 0.5) + 1)) for c in crop_size]
+        if on_device:
+            out, outs, _ = crop_box(tensor_img, vols, crop_size, pad=full, center=coordinate.to(torch.int32), offset=offs)
+        else:
+            org = [int(np.clip(int(z) - c // 2 + o, 0, f - c)) for z, c, o, f in zip(coordinate, crop_size, offs, full)]
+            out, outs, _ = crop_box(tensor_img, vols, crop_size, pad=full, origin=org)
+    else:
+        zyx = [int(v) for v in (coordinate.tolist() if isinstance(coordinate, torch.Tensor) else coordinate)]
+        if mode == 'random':
+            org = [int(np.random.randint(max(0, z - c), min(f - c, z + c))) for z, c, f in zip(zyx, crop_size, full)]
+        else:
+            org = [min(max(0, z - math.ceil(c / 2)), f - c) for z, c, f in zip(zyx, crop_size, full)]
+        out, outs, _ = crop_box(tensor_img, vols, crop_size, pad=full, origin=org)
+    res = (out, _label_like(tensor_lab, outs[0]))
+    return res + (outs[1].to(foreground.dtype),) if foreground is not None else res

@@ -3,3 +3,4 @@ from .packed import pack_bits, unpack_bits_device, ingest_packed_batch, PackedBi
 from .sampler import ChunkedSampler  # noqa: F401
 from .synthetic import SyntheticUFODataset  # noqa: F401
 from .augmented import AugmentedCropDataset, save_crop, estimate_tumor_volume  # noqa: F401
+from .whole_volume import DeviceCropper  # noqa: F401
