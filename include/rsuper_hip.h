@@ -652,6 +652,41 @@ int rsuper_crop_box(const void* img, int img_dtype, float* img_out, int B, int C
                     const int* origin, int* origin_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The report-annotated branch of the whole-CT crop -- dataset_abdomenatlas_UFO.py get_random_tumor_seg_mask :855, assign_labels :1154,
+ * get_chosen_segment_mask :808; training/augmentation.py crop_foreground_3d :790, denoise_mask :746.  No memset, no atomics, bit-reproducible; every
+ * argument is checked before anything is launched (RSUPER_ERR_ARG); any base alignment of the label and any voxel count.
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_OPEN_MAX_RADIUS 4
+#define RSUPER_REMAP_TABLE_WORDS 448
+/* packed, B, P, C, plain, D, H, W: the label of rsuper_class_counts.  sets: HOST [B] 64-bit class sets (bit c = class c; a bit at or above C ->
+ * RSUPER_ERR_ARG); a voxel is on where any class of its sample's set is.  count [B] int64 and bbox [B][6] int32 (device): the on voxels and their
+ * min z, y, x, max z, y, x; none: min = (D, H, W), max = (-1, -1, -1).  Only the planes a set touches are read.  Launch 1 writes one row of 8 int32
+ * per RSUPER_CROP_CHUNK voxels into `workspace` (device, 4-byte aligned, rsuper_union_bbox_workspace_bytes bytes), launch 2 folds them in a fixed
+ * order; one launch 1 per 8 samples. */
+long rsuper_union_bbox_workspace_bytes(int B, int D, int H, int W);
+int rsuper_union_bbox(const uint8_t* packed, int B, int P, int C, int plain, int D, int H, int W, const unsigned long long* sets, void* workspace,
+                      long workspace_bytes, long long* count, int* bbox, void* stream);
+/* The same union of sample b inside the sub-box (z0, y0, x0) + (nz, ny, nx) as bits [nz][ny][ceil(nx / 64)] u64 (device, 8-byte aligned): bit i of
+ * word k of a row is voxel x0 + 64 k + i, bits past nx are zero.  One launch, one wave per word.  A sub-box outside the volume -> RSUPER_ERR_ARG. */
+int rsuper_union_bits(const uint8_t* packed, int B, int P, int C, int plain, int D, int H, int W, int b, unsigned long long set, int z0, int y0, int x0,
+                      int nz, int ny, int nx, unsigned long long* bits, void* stream);
+/* binary_dilation(binary_erosion(m, iterations = r), iterations = r) & m of the bit volume `bits` [nz][ny][ceil(nx / 64)] (scipy's default cross,
+ * border_value = 0: zero is read outside the box), 1 <= r <= RSUPER_OPEN_MAX_RADIUS, in 2 r + 1 launches over two ping-pong copies in `workspace`
+ * (device, 8-byte aligned, rsuper_bits_open_workspace_bytes bytes).  Bits past nx in a row's last word are ignored on input.  out_bits: the result in
+ * the same layout; `bits`, out_bits and the workspace must not overlap (RSUPER_ERR_ARG); out_mask: the result as
+ * [nz][ny][nx] u8 0 / 1; count (1 int64) and bbox (6 int32), device: as rsuper_union_bbox writes them, in box coordinates + (add_z, add_y, add_x). */
+long rsuper_bits_open_workspace_bytes(int nz, int ny, int nx);
+int rsuper_bits_open(const unsigned long long* bits, int nz, int ny, int nx, int r, int add_z, int add_y, int add_x, void* workspace, long workspace_bytes,
+                     unsigned long long* out_bits, uint8_t* out_mask, long long* count, int* bbox, void* stream);
+/* in: device [B][P_in][v] u8 bit-packed as above (C_in classes, ceil(C_in / 8) <= P_in <= 8) -> nvol <= 3 volumes outs[k] [B][P_out][v] (outs: HOST
+ * array of device pointers, none of them `in`) of C_out classes, P_out = ceil(C_out / 8).  masks: HOST [B][nvol][C_out], ones: HOST [B][nvol], 64-bit:
+ * class j of volume k of sample b at a voxel = (the voxel's input classes & masks[b][k][j]) != 0 || bit j of ones[b][k]; the padding bits of the last
+ * plane are zero.  The tables travel in the kernel arguments: one launch per min(8, RSUPER_REMAP_TABLE_WORDS / (nvol * C_out)) samples.  A table bit
+ * at or above C_in (masks) or C_out (ones) -> RSUPER_ERR_ARG.  Dword loads and stores when v % 4 == 0 and the bases are 4-byte aligned. */
+int rsuper_label_remap(const uint8_t* in, int B, int P_in, int C_in, long v, int nvol, uint8_t* const* outs, int P_out, int C_out,
+                       const unsigned long long* masks, const unsigned long long* ones, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser -- train_ddp.py:352-357, training/utils.py:46-51,154-161.  host_* are HOST arrays of device pointers.
  * ------------------------------------------------------------------------------------------------ */
 /* *total_sq = sum of squared elements of the n gradient tensors (f64, deterministic order).  The accumulator need not be zeroed: the first launch

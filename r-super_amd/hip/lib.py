@@ -5,7 +5,7 @@ The product path has no CPU fallback: `lib()` raises if the shared library is mi
 """
 import ctypes
 import os
-from ctypes import c_int, c_long, c_longlong, c_size_t, c_float, c_double, c_void_p, c_uint32, c_uint
+from ctypes import c_int, c_long, c_longlong, c_size_t, c_float, c_double, c_void_p, c_uint32, c_uint, c_ulonglong
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(os.path.dirname(_HERE), 'csrc', 'librsuper_hip.so')
@@ -147,6 +147,12 @@ _SIGS = {
     'rsuper_class_counts': (c_int, [P] + [c_int] * 7 + [P, c_long, P, P]),
     'rsuper_select_voxel': (c_int, [P] + [c_int] * 7 + [P, c_long, c_int, c_int, c_long, c_long, c_int, c_int, c_int, P, P]),
     'rsuper_crop_box': (c_int, [P, c_int, P] + [c_int] * 6 + [P, P, P] + [c_int] * 6 + [P, P, P, P]),
+    'rsuper_union_bbox_workspace_bytes': (c_long, [c_int] * 4),
+    'rsuper_union_bbox': (c_int, [P] + [c_int] * 7 + [P, P, c_long, P, P, P]),
+    'rsuper_union_bits': (c_int, [P] + [c_int] * 8 + [c_ulonglong] + [c_int] * 6 + [P, P]),
+    'rsuper_bits_open_workspace_bytes': (c_long, [c_int] * 3),
+    'rsuper_bits_open': (c_int, [P] + [c_int] * 7 + [P, c_long, P, P, P, P, P]),
+    'rsuper_label_remap': (c_int, [P, c_int, c_int, c_int, c_long, c_int, P, c_int, c_int, P, P, P]),
     'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

@@ -28,6 +28,11 @@ crop-on-tumour from a whole CT (training/augmentation.py; no derivative):
     torch.ops.rsuper.class_counts(packed, C, plain, workspace) -> (totals, chunk table)
     torch.ops.rsuper.select_voxel(packed, C, plain, table, b, column, k, count, add) -> (z, y, x)
     torch.ops.rsuper.crop_box(img, volumes, size, pad, center, origin) -> (image crop, volume crops, corners)
+report-annotated crops from a whole CT (training/augmentation.py; no derivative):
+    torch.ops.rsuper.union_bbox(packed, C, plain, sets) -> count and bounding box per sample in one buffer
+    torch.ops.rsuper.union_bits(packed, C, plain, b, set, box) -> bit words of the union inside the box
+    torch.ops.rsuper.bits_open(bits, nx, r, add) -> (opened bits, u8 mask, count and bounding box)
+    torch.ops.rsuper.label_remap(packed, C_in, C_out, nvol, masks, ones) -> remapped packed volumes
 whole-case preprocessing and resampling (inference/preprocess.py, inference/resample.py; no derivative):
     torch.ops.rsuper.ct_normalize(hu, lo, hi, out_shape, offset, workspace) -> (z-scored, zero-padded volume, (mean, std))
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
@@ -211,6 +216,23 @@ def install_crop_ops(class_counts, select_voxel, crop_box):
                             crop_box),
         )
     return _CROP_OPS
+
+
+_REPORT_CROP_OPS = None
+
+
+def install_report_crop_ops(union_bbox, union_bits, bits_open, label_remap):
+    """Register the report-crop operators of training/augmentation.py (on their first use; idempotent) as plain CUDA kernels: counts, boxes, bit
+    masks and remapped labels have no derivative.  Class sets are 64-bit sets as signed ints (the schema has no unsigned type)."""
+    global _REPORT_CROP_OPS
+    if _REPORT_CROP_OPS is None:
+        _REPORT_CROP_OPS = (
+            _register_plain('union_bbox', '(Tensor packed, int C, bool plain, int[] sets) -> Tensor', union_bbox),
+            _register_plain('union_bits', '(Tensor packed, int C, bool plain, int b, int set, int[] box) -> Tensor', union_bits),
+            _register_plain('bits_open', '(Tensor bits, int nx, int r, int[] add) -> (Tensor, Tensor, Tensor)', bits_open),
+            _register_plain('label_remap', '(Tensor packed, int C_in, int C_out, int nvol, int[] masks, int[] ones) -> Tensor[]', label_remap),
+        )
+    return _REPORT_CROP_OPS
 
 
 _INTENSITY_OP = None

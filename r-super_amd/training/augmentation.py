@@ -804,3 +804,293 @@ def crop_around_coordinate_3d(tensor_img, tensor_lab, crop_size, coordinate, mod
         out, outs, _ = crop_box(tensor_img, vols, crop_size, pad=full, origin=org)
     res = (out, _label_like(tensor_lab, outs[0]))
     return res + (outs[1].to(foreground.dtype),) if foreground is not None else res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The report-annotated crop on the device (csrc/crop_report.hip): crop_foreground_3d (augmentation.py:790) and denoise_mask (:746) for a whole
+# CT whose label is a PackedBits.  The foreground of a report crop is a union of segment classes: rsuper_union_bbox gives its voxel count and
+# bounding box in one pass over the packed planes the set touches (the reference sums inflated planes and calls torch.nonzero), and only
+# when that box is larger than the crop does the opening run -- on the bits of the box alone (rsuper_union_bits, rsuper_bits_open), followed
+# by rsuper_largest_component on the box's u8 mask.  Restricting the opening to the mask's own bounding box is exact: an erosion reads zero
+# outside either way, and a dilation step can only set a voxel outside the box from a voxel inside it, which the final `& m` clears again
+# while nothing outside ever feeds back in (the L1 path between two voxels of a box stays in the box).  No CPU kernel.
+# ---------------------------------------------------------------------------------------------------------------------------
+OPEN_MAX_RADIUS = 4        # RSUPER_OPEN_MAX_RADIUS of the header
+ZERO_MASK, NO_FIT = 'zero mask', 'mask does not fit crop size'      # crop_foreground_3d's two strings (:849, :908)
+
+
+def class_set(classes):
+    """Class indices (or one 64-bit set) -> the 64-bit set the union kernels take: bit c = class c."""
+    if isinstance(classes, int):
+        return classes
+    s = 0
+    for c in classes:
+        if not 0 <= int(c) < 64:
+            raise ValueError('class_set: class %r outside [0, 64)' % (c,))
+        s |= 1 << int(c)
+    return s
+
+
+def _signed64(v):
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _count_box(B, device):
+    """One int64 buffer that holds count [B] int64 and bbox [B][6] int32, so that both come to the host in one read."""
+    buf = torch.empty((4 * B,), device=device, dtype=torch.int64)
+    return buf, buf[:B], buf[B:].view(torch.int32).view(B, 6)
+
+
+def _read_count_box(buf, B=1):
+    """-> [(count, [min z, y, x, max z, y, x])] per sample: the one device-to-host read."""
+    h = buf.cpu()
+    box = h[B:].view(torch.int32).view(B, 6).tolist()
+    return [(int(h[b]), box[b]) for b in range(B)]
+
+
+def _union_bbox(packed, C, plain, sets):
+    """The C ABI call.  packed (B, P, D, H, W) u8, sets: B ints -> the (4 B,) int64 buffer of _count_box."""
+    import ctypes
+    from ..hip import lib as _l
+    _need_device('union_bbox', packed)
+    if packed.dim() != 5 or packed.dtype != torch.uint8 or not packed.is_contiguous():
+        raise ValueError('union_bbox: the label must be contiguous uint8 (B, P, D, H, W), got %s %s' % (packed.dtype, tuple(packed.shape)))
+    B, P, D, H, W = packed.shape
+    if len(sets) != B:
+        raise ValueError('union_bbox: one class set per sample')
+    L = _l.lib()
+    ws = torch.empty((max(L.rsuper_union_bbox_workspace_bytes(B, D, H, W), 1),), device=packed.device, dtype=torch.uint8)
+    buf, count, bbox = _count_box(B, packed.device)
+    with torch.cuda.device(packed.device):
+        _l.check(L.rsuper_union_bbox(packed.data_ptr(), B, P, int(C), int(bool(plain)), D, H, W,
+                                     (ctypes.c_ulonglong * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in sets]), ws.data_ptr(), ws.numel(),
+                                     count.data_ptr(), bbox.data_ptr(), torch.cuda.current_stream().cuda_stream), 'union_bbox')
+    return buf
+
+
+def _union_bits(packed, C, plain, b, cset, box):
+    """The C ABI call.  box: (z0, y0, x0, nz, ny, nx) -> (nz, ny, ceil(nx / 64)) int64 device tensor of the bit words."""
+    from ..hip import lib as _l
+    _need_device('union_bits', packed)
+    if packed.dim() != 5 or packed.dtype != torch.uint8 or not packed.is_contiguous():
+        raise ValueError('union_bits: the label must be contiguous uint8 (B, P, D, H, W)')
+    B, P, D, H, W = packed.shape
+    z0, y0, x0, nz, ny, nx = (int(v) for v in box)
+    if min(nz, ny, nx) < 1:
+        raise ValueError('union_bits: an empty box %s' % (tuple(box),))
+    bits = torch.empty((nz, ny, (nx + 63) // 64), device=packed.device, dtype=torch.int64)
+    with torch.cuda.device(packed.device):
+        _l.check(_l.lib().rsuper_union_bits(packed.data_ptr(), B, P, int(C), int(bool(plain)), D, H, W, int(b), int(cset) & 0xFFFFFFFFFFFFFFFF,
+                                            z0, y0, x0, nz, ny, nx, bits.data_ptr(), torch.cuda.current_stream().cuda_stream), 'union_bits')
+    return bits
+
+
+def _bits_open(bits, nx, r, add):
+    """The C ABI call.  bits (nz, ny, ceil(nx / 64)) int64 -> (opened bits, (nz, ny, nx) u8 mask, the (4,) int64 count + bbox buffer)."""
+    from ..hip import lib as _l
+    _need_device('bits_open', bits)
+    nx = int(nx)
+    if bits.dim() != 3 or bits.dtype != torch.int64 or not bits.is_contiguous() or nx < 1 or bits.shape[2] != (nx + 63) // 64:
+        raise ValueError('bits_open: bits must be a contiguous int64 (nz, ny, ceil(nx / 64)) tensor')
+    nz, ny = int(bits.shape[0]), int(bits.shape[1])
+    L = _l.lib()
+    ws = torch.empty((max(L.rsuper_bits_open_workspace_bytes(nz, ny, nx), 8) // 8,), device=bits.device, dtype=torch.int64)
+    out = torch.empty_like(bits)
+    mask = torch.empty((nz, ny, nx), device=bits.device, dtype=torch.uint8)
+    buf, count, bbox = _count_box(1, bits.device)
+    with torch.cuda.device(bits.device):
+        _l.check(L.rsuper_bits_open(bits.data_ptr(), nz, ny, nx, int(r), int(add[0]), int(add[1]), int(add[2]), ws.data_ptr(), ws.numel() * 8,
+                                    out.data_ptr(), mask.data_ptr(), count.data_ptr(), bbox.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                 'bits_open')
+    return out, mask, buf
+
+
+def _label_remap(packed, C_in, C_out, nvol, masks, ones):
+    """The C ABI call.  packed (B, P_in, d, h, w) u8; masks: B * nvol * C_out ints, ones: B * nvol ints -> nvol (B, ceil(C_out / 8), d, h, w) u8."""
+    import ctypes
+    from ..hip import lib as _l
+    _need_device('label_remap', packed)
+    if packed.dim() != 5 or packed.dtype != torch.uint8 or not packed.is_contiguous():
+        raise ValueError('label_remap: the label must be contiguous uint8 (B, P, d, h, w)')
+    B, P = int(packed.shape[0]), int(packed.shape[1])
+    nvol, C_in, C_out = int(nvol), int(C_in), int(C_out)
+    if len(masks) != B * nvol * C_out or len(ones) != B * nvol or not 1 <= nvol <= 3:
+        raise ValueError('label_remap: masks must hold B * nvol * C_out sets and ones B * nvol, nvol <= 3')
+    v = packed[0, 0].numel()
+    P_out = (C_out + 7) // 8
+    outs = [torch.empty((B, P_out) + tuple(packed.shape[2:]), device=packed.device, dtype=torch.uint8) for _ in range(nvol)]
+    u = 0xFFFFFFFFFFFFFFFF
+    with torch.cuda.device(packed.device):
+        _l.check(_l.lib().rsuper_label_remap(packed.data_ptr(), B, P, C_in, v, nvol, (ctypes.c_void_p * nvol)(*[o.data_ptr() for o in outs]), P_out, C_out,
+                                             (ctypes.c_ulonglong * len(masks))(*[int(m) & u for m in masks]),
+                                             (ctypes.c_ulonglong * len(ones))(*[int(o) & u for o in ones]),
+                                             torch.cuda.current_stream().cuda_stream), 'label_remap')
+    return outs
+
+
+def _report_ops():
+    from ..hip import ops as _ops          # noqa: F401
+    from ..hip import library as _library
+    return _library.install_report_crop_ops(_union_bbox, _union_bits, _bits_open, _label_remap)
+
+
+def _mask_planes(mask, what):
+    """A device mask (D, H, W) / (1, D, H, W) -> the plain one-class label (1, 1, D, H, W) u8 of the union kernels."""
+    _need_device(what, mask)
+    if mask.dim() == 4 and mask.shape[0] == 1:
+        mask = mask[0]
+    if mask.dim() != 3:
+        raise ValueError('Foreground must be [D,H,W] or [1,D,H,W], got %s' % (tuple(mask.shape),))
+    return _as_bytes(mask, what).contiguous()[None, None]
+
+
+def union_bbox(lab, class_sets):
+    """Voxel count and bounding box of the union of the classes of `class_sets` (one per sample: a 64-bit set or class indices) of a PackedBits or
+    plain (B, C, D, H, W) label -> the device buffer `_read_count_box` turns into [(count, [min z, y, x, max z, y, x])] with one read
+    (torch.ops.rsuper.union_bbox).  No voxel: min = (D, H, W), max = (-1, -1, -1)."""
+    planes, C, plain = _label_planes(lab, 'union_bbox')
+    return _report_ops()[0](planes, C, plain, [_signed64(class_set(s)) for s in class_sets])
+
+
+def union_bits(lab, cset, box, b=0):
+    """The union of the classes of `cset` of sample b inside box = (z0, y0, x0, nz, ny, nx) as (nz, ny, ceil(nx / 64)) int64 bit words: bit i of word
+    k is voxel x0 + 64 k + i (torch.ops.rsuper.union_bits)."""
+    planes, C, plain = _label_planes(lab, 'union_bits')
+    return _report_ops()[1](planes, C, plain, int(b), _signed64(class_set(cset)), [int(v) for v in box])
+
+
+def bits_open(bits, nx, iterations, add=(0, 0, 0)):
+    """binary_dilation(binary_erosion(m, iterations), iterations) & m of a bit volume, zero outside (torch.ops.rsuper.bits_open) -> (bits, (nz, ny,
+    nx) u8 mask, count + bbox buffer in box coordinates + add)."""
+    if not 1 <= int(iterations) <= OPEN_MAX_RADIUS:
+        raise ValueError('bits_open: 1 <= iterations <= %d, got %r' % (OPEN_MAX_RADIUS, iterations))
+    return _report_ops()[2](bits, int(nx), int(iterations), [int(v) for v in add])
+
+
+def label_remap(lab, C_out, masks, ones):
+    """lab: PackedBits (B, C_in, d, h, w); masks [B][nvol][C_out] and ones [B][nvol] as nested lists of 64-bit sets -> nvol PackedBits of C_out classes:
+    class j of volume k = (the voxel's classes & masks[b][k][j]) != 0 or bit j of ones[b][k] (torch.ops.rsuper.label_remap)."""
+    nvol = len(ones[0])
+    flat_m = [_signed64(m) for sample in masks for vol in sample for m in vol]
+    flat_o = [_signed64(o) for sample in ones for o in sample]
+    outs = _report_ops()[3](lab.packed, lab.C, int(C_out), nvol, flat_m, flat_o)
+    return tuple(type(lab)(o, int(C_out)) for o in outs)
+
+
+def _open_box(planes, C, plain, cset, box, lo_corner, iterations, connected_component=True):
+    """The opening of the union inside its bounding box `box` = [min z, y, x, max z, y, x] (real coordinates), then the largest component.
+    -> (count, bbox in coordinates + lo_corner, (nz, ny, nx) u8 mask of the box), count == 0: nothing is left.  Two device-to-host reads at the most:
+    the opening's count (the largest-component kernel answers all ones for an empty mask, so it must not run on one) and the component's box."""
+    from ..inference.postprocess import keep_largest_component
+    z0, y0, x0 = box[:3]
+    nz, ny, nx = (box[3 + i] - box[i] + 1 for i in range(3))
+    add = [z0 + lo_corner[0], y0 + lo_corner[1], x0 + lo_corner[2]]
+    bits = _report_ops()[1](planes, C, plain, 0, _signed64(cset), [z0, y0, x0, nz, ny, nx])
+    _, mask, buf = _report_ops()[2](bits, nx, int(iterations), add)
+    (count, bbox), = _read_count_box(buf)
+    if count == 0 or not connected_component:
+        return count, bbox, mask
+    mask = keep_largest_component(mask)
+    (count, bbox), = _read_count_box(_report_ops()[0](mask[None, None], 1, True, [1]))
+    return count, [v + add[i % 3] for i, v in enumerate(bbox)], mask
+
+
+def denoise_mask(mask_3d, iterations=2, connected_component=True):
+    """denoise_mask (:746-787) on a device mask (D, H, W): `iterations` erosions and dilations with scipy's cross, AND with the mask, then the largest
+    face-connected component (ties: the first in C order, as np.argmax over ndimage.label's counts).  -> bool (D, H, W) on the device."""
+    planes = _mask_planes(mask_3d, 'denoise_mask')
+    (count, box), = _read_count_box(_report_ops()[0](planes, 1, True, [1]))
+    out = torch.zeros(tuple(planes.shape[2:]), device=planes.device, dtype=torch.bool)
+    if count == 0:
+        return out
+    count, _, sub = _open_box(planes, 1, True, 1, box, [0, 0, 0], iterations, connected_component)
+    if count:
+        out[box[0]:box[3] + 1, box[1]:box[4] + 1, box[2]:box[5] + 1] = sub.bool()
+    return out
+
+
+def bbox_with_margin(bbox, size, margin=1):
+    """[min z, y, x, max z, y, x] widened by the margin and clamped to the volume, with the reference's swaps (:857-872)."""
+    margin = (margin,) * 3 if isinstance(margin, int) else tuple(margin)
+    lo = [max(int(bbox[i]) - margin[i], 0) for i in range(3)]
+    hi = [min(int(bbox[3 + i]) + margin[i], int(size[i]) - 1) for i in range(3)]
+    for i in range(3):
+        if lo[i] > hi[i]:
+            lo[i], hi[i] = hi[i], lo[i]
+    return lo + hi
+
+
+def bbox_fits(box, crop_size):
+    return all(box[3 + i] - box[i] + 1 <= int(crop_size[i]) for i in range(3))
+
+
+def plan_crop_foreground(bbox, size, crop_size, margin=1, rand=True):
+    """The host part of crop_foreground_3d after the bounding box is known (:857-966): margin, clamp and swaps, the size test, valid_shifts_1D, and the
+    random.randint draws in z, y, x order (rand=False: the middle of the range).  bbox: [min z, y, x, max z, y, x] of the foreground in the
+    coordinates of `size`.  -> the crop's corner [z, y, x], or 'mask does not fit crop size'."""
+    import random
+    box = bbox_with_margin(bbox, size, margin)
+    if not bbox_fits(box, crop_size):
+        return NO_FIT
+    rng = []
+    for i in range(3):
+        low = max(box[3 + i] - (int(crop_size[i]) - 1), 0)
+        high = min(box[i], int(size[i]) - int(crop_size[i]))
+        rng.append((int(low), int(high)))
+    if any(low > high for low, high in rng):
+        return NO_FIT
+    return [random.randint(low, high) if rand else (low + high) // 2 for low, high in rng]
+
+
+def crop_foreground_3d(tensor_ct, tensor_lab, foreground, crop_size, margin=1, refine_iterations=3, rand=True, pad=None, count_box=None):
+    """crop_foreground_3d (:790-1019) on a device volume (1, 1, D, H, W) f32 / int16 and a PackedBits or plain (1, C, D, H, W) label.  foreground: a
+    device mask (D, H, W) / (1, D, H, W), or the classes of tensor_lab whose union it is (a 64-bit set or class indices; PackedBits label).  All
+    coordinates are those of the volume padded to `pad` as pad_volume_pair pads (no padded copy is made).  -> (image crop, label crop of
+    tensor_lab's kind, bool (d, h, w) crop of the foreground, or of the refined mask when the opening ran), or 'zero mask' /
+    'mask does not fit crop size'.  One device-to-host read, three when the opening runs; count_box: the (count, box) of the foreground when the
+    caller has already read it."""
+    _need_device('crop_foreground_3d', tensor_ct)
+    if tensor_ct.dim() != 5 or tensor_ct.shape[0] != 1 or tensor_ct.shape[1] != 1:
+        raise ValueError('CT must be [1,1,D,H,W], got %s' % (tuple(tensor_ct.shape),))
+    planes, C, plain = _label_planes(tensor_lab, 'crop_foreground_3d')
+    size = tuple(tensor_ct.shape[2:])
+    if tuple(planes.shape[2:]) != size:
+        raise ValueError('The input and label tensors must have the same spatial dimensions.')
+    crop = [int(c) for c in ([crop_size] * 3 if isinstance(crop_size, int) else crop_size)]
+    full, lo = padded_size(size, pad)
+    if any(c > f for c, f in zip(crop, full)):
+        raise ValueError('crop %s is larger than the (padded) volume %s' % (crop, full))
+    if isinstance(foreground, torch.Tensor):
+        fplanes, fC, fplain, cset = _mask_planes(foreground, 'crop_foreground_3d'), 1, True, 1
+        if tuple(fplanes.shape[2:]) != size:
+            raise ValueError('The foreground must be on the image grid')
+    else:
+        fplanes, fC, fplain, cset = planes, C, plain, class_set(foreground)
+    count, box = count_box if count_box is not None else _read_count_box(_report_ops()[0](fplanes, fC, fplain, [_signed64(cset)]))[0]
+    if count == 0:
+        return ZERO_MASK
+    padded_box = [v + lo[i % 3] for i, v in enumerate(box)]
+    refined = None
+    if not bbox_fits(bbox_with_margin(padded_box, full, margin), crop):
+        count, padded_box, refined = _open_box(fplanes, fC, fplain, cset, box, lo, refine_iterations)
+        if count == 0:
+            return ZERO_MASK
+    corner = plan_crop_foreground(padded_box, full, crop, margin, rand)
+    if isinstance(corner, str):
+        return corner
+    vols = [planes] if refined is not None or fplain is False or fplanes is planes else [planes, fplanes[:, 0:1]]
+    img, outs, _ = crop_box(tensor_ct, vols, crop, pad=full, origin=corner)
+    if refined is not None:
+        fg = torch.zeros(crop, device=planes.device, dtype=torch.bool)
+        o = [box[i] + lo[i] - corner[i] for i in range(3)]                   # the box's origin in the crop
+        a = [max(0, -o[i]) for i in range(3)]
+        e = [min(refined.shape[i], crop[i] - o[i]) for i in range(3)]
+        fg[o[0] + a[0]:o[0] + e[0], o[1] + a[1]:o[1] + e[1], o[2] + a[2]:o[2] + e[2]] = refined[a[0]:e[0], a[1]:e[1], a[2]:e[2]].bool()
+    elif len(vols) == 2:
+        fg = outs[1][0, 0] != 0
+    elif plain:
+        fg = (outs[0][0] != 0)[[c for c in range(C) if cset >> c & 1]].any(0)
+    else:
+        fg = _report_ops()[3](outs[0].contiguous(), C, 1, 1, [_signed64(cset)], [0])[0][0, 0] != 0
+    return img, _label_like(tensor_lab, outs[0]), fg
