@@ -477,6 +477,13 @@ int rsuper_mask_op(uint8_t* a, const uint8_t* b, long V, int op /*0 and, 1 or, 2
  * segment volumes the dataset stores with np.packbits(axis=0) -- training/dataset/dim3/dataset_abdomenatlas_UFO.py:955,
  * 970,975 (pack), :1031-1034 (unpack).  packed: [B][P = ceil(C/8)][V] bytes (MSB = lowest class), out: [B][C][V] 0/1. */
 int rsuper_unpack_bits(const uint8_t* packed, uint8_t* out, int B, int P, int C, long V, void* stream);
+/* The inverse: device-side np.packbits(src != 0, axis = class) of the unpacked int8 / uint8 / bool (C, D, H, W) label the dataset converter writes
+ * (dataset_conversion/nii2npz.py:80-82; the dataset accepts both forms, dataset_abdomenatlas_UFO.py:465-470).  src: B * C one-byte planes of V voxels, plane
+ * (b, c) at src + (b * C + c) * src_plane_stride; any non-zero byte counts as 1.  dst: B * P byte planes, P = ceil(C / 8), plane (b, p) at
+ * dst + (b * P + p) * dst_plane_stride; class c is bit 7 - (c & 7) of plane c >> 3, the unused low bits of the last plane are 0.  Both strides are in bytes and
+ * >= V: a z-slab in a staging buffer is packed straight into its place of the whole packed volume.  Nothing at or past V of a plane is read or written.
+ * 16-byte vectors when both pointers and both strides are multiples of 16, bytes otherwise.  B * P <= 65535. */
+int rsuper_pack_bits(const uint8_t* src, uint8_t* dst, int B, int C, long V, long src_plane_stride, long dst_plane_stride, void* stream);
 /* Timing events for SURVEY 8(d)'s per-launch measurement (bench.py's roofline pass: HIP events around every conv MFMA launch, on the launch stream): events
  * created with hipEventDisableSystemFence -- a default event performs a system-scope release (cache write-back + invalidate) when recorded, which is charged to the
  * bracket and leaves the next kernel a cold L2; the HIP header recommends the flag for events that only measure time.  elapsed_ms waits for `b`. */

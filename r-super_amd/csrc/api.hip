@@ -716,6 +716,10 @@ int rsuper_unpack_bits(const uint8_t* packed, uint8_t* out, int B, int P, int C,
     if (!packed || !out || B <= 0 || P <= 0 || C <= 0 || C > 8 * P || V <= 0) return RS_ERR_ARG;
     return rs_launch_unpack_bits(packed, out, B, P, C, V, ST(stream));
 }
+int rsuper_pack_bits(const uint8_t* src, uint8_t* dst, int B, int C, long V, long src_plane_stride, long dst_plane_stride, void* stream) {
+    if (!src || !dst || B <= 0 || C <= 0 || V <= 0 || src_plane_stride < V || dst_plane_stride < V || (long)B * ((C + 7) / 8) > 65535) return RS_ERR_ARG;
+    return rs_launch_pack_bits(src, dst, B, C, V, src_plane_stride, dst_plane_stride, ST(stream));
+}
 // ---- timing events of the roofline pass (bench.py, ops.KernelTimer).  hipEventDisableSystemFence: an event of the default kind performs a system-scope release when
 // it is recorded -- cache write-back + invalidate between every pair of launches it brackets, which both costs time inside the bracket and makes the NEXT kernel start
 // on a cold L2 (packed weight fragments, halo rows shared with the previous launch).  hip_runtime_api.h: "can be used for events that are only being used to measure

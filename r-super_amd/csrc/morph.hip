@@ -786,6 +786,62 @@ int rs_launch_unpack_bits(const uint8_t* packed, uint8_t* out, int B, int P, int
     return rs_check_launch();
 }
 
+// The inverse, np.packbits((src != 0), axis = class) on the device: dst[b][p][v] = OR_k (src[b][8 p + k][v] != 0) << (7 - k), classes >= C contribute 0.
+// What the dataset converter writes is the unpacked int8 (C, D, H, W) volume (dataset_conversion/nii2npz.py:80-82); the croppers read the packed form.
+// The two plane strides (bytes, >= V) let a z-slab held in a staging buffer be packed straight into its place of the whole packed volume.
+// nz4: per byte of a dword, 1 when the byte is non-zero (bit 7 of ((x & 0x7f..) + 0x7f..) | x is set exactly then; no carry leaves a byte).
+__device__ __forceinline__ uint32_t nz4(uint32_t x) { return ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) >> 7) & 0x01010101u; }
+
+// VEC: every plane of src and dst starts 16-byte aligned (bases and strides are multiples of 16).  Thread = 16 voxels of one byte plane: up to eight 16-byte
+// loads, one 16-byte store; the V % 16 tail of a plane goes byte by byte and nothing is read or written at or past V.
+// !VEC (an unaligned base or stride): thread = 1 voxel, up to eight byte loads (lanes read consecutive bytes), one byte store.
+template <bool VEC>
+__global__ __launch_bounds__(256) void pack_bits_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int P, int C, long V, long sstride, long dstride) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const int pl = blockIdx.y % P, b = blockIdx.y / P;
+    const int nk = min(8, C - pl * 8);                             // wave-uniform
+    const uint8_t* s = src + ((size_t)b * C + (size_t)pl * 8) * (size_t)sstride;
+    uint8_t* d = dst + ((size_t)b * P + pl) * (size_t)dstride;
+    if (VEC) {
+        const long v0 = t * 16;
+        if (v0 >= V) return;
+        if (v0 + 16 <= V) {
+            uint4 o = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (k < nk) {
+                    const uint4 x = *(const uint4*)(s + (size_t)k * (size_t)sstride + v0);
+                    o.x |= nz4(x.x) << (7 - k); o.y |= nz4(x.y) << (7 - k); o.z |= nz4(x.z) << (7 - k); o.w |= nz4(x.w) << (7 - k);
+                }
+            }
+            *(uint4*)(d + v0) = o;
+        } else {
+            for (long v = v0; v < V; ++v) {
+                unsigned o = 0;
+                for (int k = 0; k < nk; ++k) o |= (unsigned)(s[(size_t)k * (size_t)sstride + v] != 0) << (7 - k);
+                d[v] = (uint8_t)o;
+            }
+        }
+    } else {
+        if (t >= V) return;
+        unsigned o = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k < nk) o |= (unsigned)(s[(size_t)k * (size_t)sstride + t] != 0) << (7 - k);
+        d[t] = (uint8_t)o;
+    }
+}
+
+int rs_launch_pack_bits(const uint8_t* src, uint8_t* dst, int B, int C, long V, long sstride, long dstride, hipStream_t st) {
+    const int P = (C + 7) / 8;
+    const bool vec = !(((uintptr_t)src | (uintptr_t)dst | (uintptr_t)sstride | (uintptr_t)dstride) & 15);
+    const long nthr = vec ? (V + 15) / 16 : V;
+    const dim3 grid((unsigned)((nthr + 255) / 256), (unsigned)(B * P));
+    if (vec) hipLaunchKernelGGL(pack_bits_kernel<true>, grid, dim3(256), 0, st, src, dst, P, C, V, sstride, dstride);
+    else hipLaunchKernelGGL(pack_bits_kernel<false>, grid, dim3(256), 0, st, src, dst, P, C, V, sstride, dstride);
+    return rs_check_launch();
+}
+
 __global__ void plane_flags_zero_kernel(uint8_t* flags, long planes);
 
 // The same inflation for SOME class planes only: plane (b, c) is written iff flags[b * C + c] != 0 or force[c] != 0 (either table may be null; both null = every

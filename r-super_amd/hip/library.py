@@ -33,6 +33,8 @@ report-annotated crops from a whole CT (training/augmentation.py; no derivative)
     torch.ops.rsuper.union_bits(packed, C, plain, b, set, box) -> bit words of the union inside the box
     torch.ops.rsuper.bits_open(bits, nx, r, add) -> (opened bits, u8 mask, count and bounding box)
     torch.ops.rsuper.label_remap(packed, C_in, C_out, nvol, masks, ones) -> remapped packed volumes
+whole-CT label upload (training/dataset/packed.py; no derivative):
+    torch.ops.rsuper.pack_bits(volume) -> np.packbits(volume != 0, axis = class) of a one-byte (B, C, ...) volume
 whole-case preprocessing and resampling (inference/preprocess.py, inference/resample.py; no derivative):
     torch.ops.rsuper.ct_normalize(hu, lo, hi, out_shape, offset, workspace) -> (z-scored, zero-padded volume, (mean, std))
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
@@ -233,6 +235,18 @@ def install_report_crop_ops(union_bbox, union_bits, bits_open, label_remap):
             _register_plain('label_remap', '(Tensor packed, int C_in, int C_out, int nvol, int[] masks, int[] ones) -> Tensor[]', label_remap),
         )
     return _REPORT_CROP_OPS
+
+
+_PACK_OP = None
+
+
+def install_pack_ops(pack_bits):
+    """Register the label packing operator of training/dataset/packed.py (on its first use; idempotent) as a plain CUDA kernel: packed label bits have
+    no derivative."""
+    global _PACK_OP
+    if _PACK_OP is None:
+        _PACK_OP = _register_plain('pack_bits', '(Tensor volume) -> Tensor', pack_bits)
+    return _PACK_OP
 
 
 _INTENSITY_OP = None

@@ -291,12 +291,18 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
     intensity_gpu = getattr(args, 'intensity_aug_device', 'cpu') == 'gpu'
     if aug_gpu and not packed:
         raise ValueError('--aug_device gpu resamples the bit-packed volumes: the dataset must deliver packed crops (packed=True)')
+    on_device = hasattr(trainLoader, 'prefetch_next')      # dataset/whole_ct.py WholeVolumeLoader: the batch is already the device dictionary
+    if on_device and not intensity_gpu:
+        raise ValueError('training from whole CTs has no host intensity stage: pass --intensity_aug_device gpu (the six transforms then run on the device); '
+                         'they are never skipped silently')
     for i, inputs in enumerate(trainLoader):
         batch = dict(image=inputs['image'], label=inputs['label'], unk_channels=inputs['unk_channels'],
                      volumes=inputs['volumes'].float(), mask=inputs['mask'], diameters=inputs['diameters'].float())
         if 'weights' in inputs:
             batch['weights'] = inputs['weights'].float()
-        if packed:      # bit-packed label volumes cross PCIe as stored and are inflated on the device (dataset/packed.py)
+        if on_device:   # cut at training_size by DeviceCropper, its affine branch included: the spatial augmentation must not run again
+            batch['image'] = intensity_augment_batch(batch['image'])
+        elif packed:      # bit-packed label volumes cross PCIe as stored and are inflated on the device (dataset/packed.py)
             # the three volumes never leave their packed form: the loss kernels read the label bits, the report losses inflate the lesion planes they index
             # and take the unknown map's plane flags from the packed bytes (calculate_loss) -- with and without report supervision
             batch = ingest_packed_batch(batch, len(classes), dev, keep_packed=True)
@@ -325,6 +331,8 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
             loss_all, _ = train_step(use, ema_net, optimizer, batch, args, classes, step, matcher=matcher)
         if guard is not None:
             guard.end_step()
+        if on_device:   # the step is queued: queue the next batch's upload and crop on the loader's side stream before the host waits for the loss
+            trainLoader.prefetch_next()
         if len(loss_meters) == 0:
             loss_meters = OrderedDict((k, AverageMeter(k, ':6.4f')) for k in loss_all.keys())
             loss_meters['Elapsed Time'] = AverageMeter('Elapsed Time', ':6.2f')
@@ -417,7 +425,19 @@ def get_parser(argv=None, config_root=None):
                              "random_crop runs on the device (training/augmentation.py spatial_augment_batch); 'cpu' (default): crops arrive augmented")
     parser.add_argument('--intensity_aug_device', type=str, default=None, choices=['cpu', 'gpu'],
                         help="'gpu': the loader delivers crops without the six online intensity transforms and they run on the device, per sample, before "
-                             "the spatial augmentation (training/augmentation.py intensity_augment_batch); 'cpu' (default): the loader's workers apply them")
+                             "the spatial augmentation (training/augmentation.py intensity_augment_batch); 'cpu' (default): the loader's workers apply them. "
+                             "Training from whole CTs (neither --load_augmented nor --synthetic) has no host intensity stage: 'cpu' raises there")
+    parser.add_argument('--all_train', action='store_true', help='no test split: every case trains (:407)')
+    parser.add_argument('--crop_on_tumor', action='store_true', help='training from whole CTs: crop on tumours / organs (:408); without it the crop-on-tumour result goes through random_crop')
+    parser.add_argument('--save_augmented', action='store_true', help='accepted for the reference\'s command lines (:416); crops are written by python -m rsuper_amd.augment_eternal')
+    parser.add_argument('--ucsf_ids', type=str, default=None, help='csv with the report-supervised ids to use (:420)')
+    parser.add_argument('--gpu', type=str, default='0,1,2,3', help='accepted (:446); device selection stays with the launcher')
+    parser.add_argument('--pancreas_only', action='store_true')
+    parser.add_argument('--kidney_only', action='store_true')
+    parser.add_argument('--UFO_only', action='store_true', help='report-supervised volumes only (:461)')
+    parser.add_argument('--Atlas_only', action='store_true', help='per-voxel-annotated volumes only (:462)')
+    parser.add_argument('--tumor_classes', nargs='+', default=None, help='list of tumor types to process (:468)')
+    parser.add_argument('--no_prefetch', action='store_true', help='rsuper_amd extension: whole-CT loader without the one-step prefetch on a side stream')
     parser.add_argument('--synthetic', type=int, default=0, help='rsuper_amd extension: train on N synthetic samples (no dataset on disk)')
     args = parser.parse_args(argv)
     if args.aug_device is None:
@@ -481,8 +501,14 @@ def train_net(net, trainset, testset, args, ema_net=None, fold_idx=0, writer=Non
     ngpus = getattr(args, 'ngpus_per_node', 1)
     sampler = ChunkedSampler(dataset_size=leng, samples_per_epoch=args.iter_per_epoch * args.batch_size * ngpus, shuffle=True, seed=42,
                              rank=dist.get_rank() if distributed else 0, world_size=dist.get_world_size() if distributed else 1)
-    loader = data.DataLoader(trainset, batch_size=args.batch_size, shuffle=False, sampler=sampler, pin_memory=(args.aug_device != 'gpu'),
-                             num_workers=args.num_workers, persistent_workers=(args.num_workers > 0))
+    from .training.dataset.whole_ct import WholeVolumeDataset, WholeVolumeLoader
+    whole = isinstance(trainset, WholeVolumeDataset)
+    if whole:
+        loader = WholeVolumeLoader(trainset, batch_size=args.batch_size, sampler=sampler, num_workers=args.num_workers,
+                                   prefetch=not getattr(args, 'no_prefetch', False))
+    else:
+        loader = data.DataLoader(trainset, batch_size=args.batch_size, shuffle=False, sampler=sampler, pin_memory=(args.aug_device != 'gpu'),
+                                 num_workers=args.num_workers, persistent_workers=(args.num_workers > 0))
     optimizer = get_optimizer(args, net)
     cp_dir = os.path.join(args.cp_path, args.dataset, args.unique_name)
     if getattr(args, 'resume', False):
@@ -493,7 +519,8 @@ def train_net(net, trainset, testset, args, ema_net=None, fold_idx=0, writer=Non
     test_loader = None
     val_freq = getattr(args, 'val_freq', 10 ** 9)
     if testset is not None and val_freq <= args.epochs:
-        test_loader = data.DataLoader(testset, batch_size=1, shuffle=False, num_workers=0)
+        test_loader = WholeVolumeLoader(testset, batch_size=1, prefetch=False) if isinstance(testset, WholeVolumeDataset) else \
+            data.DataLoader(testset, batch_size=1, shuffle=False, num_workers=0)
     best = None
     for epoch in range(args.start_epoch, args.epochs):
         sampler.set_epoch(epoch)
@@ -606,10 +633,40 @@ def load_label_names(args, root_attr='data_root', required=True):
         return sorted(yaml.load(f, Loader=yaml.SafeLoader))
 
 
+def build_datasets(args):
+    """get_dataset (training/dataset/utils.py:3-87) for the two whole-CT datasets -> (trainset, testset).  `abdomenatlas`: the annotated root alone;
+    `abdomenatlas_ufo`: both roots and the reports.  The reference's errors for --pancreas_only / --kidney_only / --UFO_only / --Atlas_only with
+    another dataset, and for a dataset it does not know.  With --all_train there is no test set."""
+    from .training.dataset.whole_ct import WholeVolumeDataset
+    g = lambda k, d=None: getattr(args, k, d)
+    if (g('pancreas_only') or g('kidney_only')) and args.dataset != 'abdomenatlas_ufo':
+        raise ValueError('Not Implemented: pancreas_only and kidney_only can only be used with abdomenatlas_ufo dataset')
+    if (g('UFO_only') or g('Atlas_only')) and args.dataset != 'abdomenatlas_ufo':
+        raise ValueError('Not Implemented: Atlas_only and UFO_only can only be used with abdomenatlas_ufo dataset')
+    if args.dimension != '3d' or args.dataset not in ('abdomenatlas', 'abdomenatlas_ufo'):
+        raise ValueError("The specified dataset doesn't exist: %s" % args.dataset)
+    if g('data_root') is None:
+        raise ValueError('training from whole CTs needs --data_root (or --load_augmented --save_destination DIR, or --synthetic N)')
+    kw = dict(seed=g('split_seed', 0), all_train=bool(g('all_train')), crop_on_tumor=bool(g('crop_on_tumor')))
+    if args.dataset == 'abdomenatlas':
+        if g('UFO_root') is not None or g('reports') is not None:
+            args = copy.copy(args)
+            args.UFO_root = args.reports = None
+    else:
+        tumor_classes = ['pancreas'] if g('pancreas_only') else ['kidney'] if g('kidney_only') else g('tumor_classes')
+        if tumor_classes is not None:
+            kw['tumor_classes'] = tumor_classes
+        kw.update(UFO_only=bool(g('UFO_only')), Atlas_only=bool(g('Atlas_only')))
+    trainset = WholeVolumeDataset(args, mode='train', **kw)
+    testset = None if kw['all_train'] else WholeVolumeDataset(args, mode='test', **kw)
+    return trainset, testset
+
+
 def main(argv=None):
     args = get_parser(argv)
     logging.basicConfig(level=logging.INFO, format='%(message)s')
     from .training.dataset import SyntheticUFODataset, AugmentedCropDataset
+    testset = None
     if args.synthetic:
         names = [f'organ_{i}' for i in range(args.classes - 2)] + ['pancreas', 'pancreatic_lesion']
         gpu_aug = args.aug_device == 'gpu'
@@ -619,10 +676,9 @@ def main(argv=None):
         # --intensity_aug_device gpu: the workers only read files, the six intensity transforms run in train_epoch
         trainset = AugmentedCropDataset.from_directory(args.save_destination, load_label_names(args), packed=True, augment=args.intensity_aug_device != 'gpu',
                                                        classes_ufo=load_label_names(args, 'UFO_root', required=False))
-    else:
-        raise SystemExit('rsuper_amd.train_ddp trains from pre-saved crops: pass --load_augmented --save_destination DIR '
-                         '(or --synthetic N for a smoke run); cropping raw volumes is offline preprocessing (INTEGRATION.md)')
-    return main_worker(int(os.environ.get('LOCAL_RANK', 0)), max(torch.cuda.device_count(), 1), 0, args, trainset=trainset)
+    else:           # whole CTs: the workers read files, the training process crops on the device (training/dataset/whole_ct.py)
+        trainset, testset = build_datasets(args)
+    return main_worker(int(os.environ.get('LOCAL_RANK', 0)), max(torch.cuda.device_count(), 1), 0, args, trainset=trainset, testset=testset)
 
 
 if __name__ == '__main__':

@@ -52,14 +52,18 @@ def crop_paths(save_destination, img_path, lab_path):
             'csv': img.replace('.npy', '.csv')}
 
 
-def save_crop(save_destination, img_path, lab_path, image, label, unk_channels=None, mask=None, meta=None, report_rows=None):
+def save_crop(save_destination, img_path, lab_path, image, label, unk_channels=None, mask=None, meta=None, report_rows=None, tumor_volumes=None,
+              tumor_diameters=None):
     """Write one crop in the on-disk format above (the writer side, :937-992).  `image` (1, D, H, W) float; `label`,
-    `unk_channels`, `mask` (C, D, H, W) 0/1; `meta` the json dict (needs 'tumor_in_crop' for report samples); `report_rows`
-    a list of dicts or a DataFrame."""
+    `unk_channels`, `mask` (C, D, H, W) 0/1 or a one-sample `PackedBits` (written as it is: same file, dtype and shape); `meta` the json dict (needs 'tumor_in_crop' for report samples); `report_rows`
+    a list of dicts or a DataFrame; `tumor_volumes` (list) and `tumor_diameters` ((10, 3) tensor or nested list) go to the two json side files of :983-990."""
     os.makedirs(save_destination, exist_ok=True)
     p = crop_paths(save_destination, img_path, lab_path)
 
     def packed(v):
+        if hasattr(v, 'packed'):               # PackedBits of one sample: its bytes are the file's contents already
+            assert v.packed.shape[0] == 1, 'save_crop writes one sample'
+            return v.packed[0].cpu().numpy()
         v = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
         return np.packbits(v.astype(np.bool_), axis=0)
 
@@ -73,6 +77,12 @@ def save_crop(save_destination, img_path, lab_path, image, label, unk_channels=N
     if meta is not None:
         with open(p['json'], 'w') as f:
             json.dump(meta, f)
+    if tumor_volumes is not None:
+        with open(p['json'].replace('.json', '_tumor_volumes.json'), 'w') as f:
+            json.dump(list(tumor_volumes), f)
+    if tumor_diameters is not None:
+        with open(p['json'].replace('.json', '_tumor_diameters.json'), 'w') as f:
+            json.dump(tumor_diameters.cpu().numpy().tolist() if isinstance(tumor_diameters, torch.Tensor) else tumor_diameters, f)
     if report_rows is not None:
         import pandas as pd
         (report_rows if isinstance(report_rows, pd.DataFrame) else pd.DataFrame(list(report_rows))).to_csv(p['csv'], index=False)

@@ -7,6 +7,8 @@ before the H2D copy (train_ddp.py:249-261): 26 x 96^3 x (8 + 4 + 4) bytes per sa
 (ceil(C/8) bytes per voxel and volume: 16x..64x less PCIe traffic) and are inflated on the device by the HIP kernel
 `rsuper_unpack_bits` into the uint8 0/1 masks `calculate_loss` consumes directly.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -35,6 +37,117 @@ def unpack_bits_device(packed, num_classes, stream=None):
     st = torch.cuda.current_stream().cuda_stream if stream is None else stream
     _l.check(_l.lib().rsuper_unpack_bits(packed.data_ptr(), out.data_ptr(), B, P, num_classes, V, st), 'unpack_bits')
     return out
+
+
+_ONE_BYTE = (torch.uint8, torch.int8, torch.bool)
+_PACK_OP = None
+
+
+def _pack_bits_impl(volume):
+    """The C ABI call.  volume (B, C, ...) one-byte device tensor -> (B, ceil(C / 8), ...) uint8, np.packbits(volume != 0, axis=1)."""
+    if not volume.is_cuda:
+        raise _l.RSuperHipError('pack_bits needs a device tensor (no CPU fallback)')
+    if volume.dim() < 3 or volume.dtype not in _ONE_BYTE:
+        raise ValueError('pack_bits: the volume must be an int8 / uint8 / bool (B, C, ...) tensor, got %s %s' % (volume.dtype, tuple(volume.shape)))
+    v = volume.contiguous()
+    B, C = v.shape[:2]
+    V = v[0, 0].numel()
+    out = torch.empty((B, (C + 7) // 8) + tuple(v.shape[2:]), device=v.device, dtype=torch.uint8)
+    with torch.cuda.device(v.device):
+        _l.check(_l.lib().rsuper_pack_bits(v.data_ptr(), out.data_ptr(), B, C, V, V, V, torch.cuda.current_stream().cuda_stream), 'pack_bits')
+    return out
+
+
+def _pack_op():
+    global _PACK_OP
+    if _PACK_OP is None:
+        from ...hip import ops as _ops          # noqa: F401  (hip/ops.py pulls in hip/library.py; this order avoids the import cycle)
+        from ...hip import library as _library
+        _PACK_OP = _library.install_pack_ops(_pack_bits_impl)
+    return _PACK_OP
+
+
+def pack_bits_device(volume):
+    """volume: int8 / uint8 / bool device tensor (B, C, D, H, W) or (C, D, H, W); any non-zero byte counts as 1 (`astype(np.bool_)`, :952) ->
+    PackedBits, the bytes np.packbits(volume != 0, axis = class) gives (torch.ops.rsuper.pack_bits, csrc/morph.hip pack_bits_kernel)."""
+    if not isinstance(volume, torch.Tensor) or not volume.is_cuda:
+        raise _l.RSuperHipError('pack_bits_device needs a device tensor (no CPU fallback)')
+    if volume.dim() == 4:
+        volume = volume.unsqueeze(0)
+    assert volume.dim() == 5 and volume.dtype in _ONE_BYTE, 'volume must be a one-byte (B, C, D, H, W) tensor'
+    return PackedBits(_pack_op()(volume), volume.shape[1])
+
+
+UPLOAD_CHUNK_BYTES = 8 << 20        # unpacked label bytes per staged z-slab of upload_label: 8 and 16 MiB were the fastest of the sizes tried (DESIGN 6j)
+_COPY_STREAMS = {}
+
+
+def _copy_stream(device):
+    s = _COPY_STREAMS.get(device)
+    if s is None:
+        s = _COPY_STREAMS[device] = torch.cuda.Stream(device=device)
+    return s
+
+
+def slab_depth(C, D, H, W, chunk_bytes):
+    """z-rows per staged slab: as many as chunk_bytes holds (at least one), rounded down to a depth whose voxel count is a multiple of 16 where that
+    is possible, so that every slab lands 16-byte aligned in the packed volume and takes the kernel's vector path."""
+    n = max(1, min(D, int(chunk_bytes) // max(1, C * H * W)))
+    q = 16 // math.gcd(H * W, 16)
+    if n < D and n >= q:
+        n -= n % q
+    return n
+
+
+def upload_label(np_lab, num_classes, device='cuda', chunk_bytes=UPLOAD_CHUNK_BYTES):
+    """A whole-CT label as the file holds it -> PackedBits (1, P, D, H, W) on `device`.  The dataset accepts two forms (:465-470): already bit-packed
+    (`shape[0] != num_classes`; the reference's `< num_classes + 10` assert) -- a plain upload; or unpacked one-byte (C, D, H, W) as
+    dataset_conversion/nii2npz.py writes it -- z-slabs go through two pinned staging buffers on a copy stream and rsuper_pack_bits packs each slab from
+    its device staging buffer straight into its place of the (P, D, H, W) result, so neither side ever holds the inflated volume whole: the device
+    footprint is the packed result plus two slabs.  The current stream waits for the copy stream before the function returns."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _l.RSuperHipError('upload_label needs a device (no CPU fallback)')
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    pinned = np_lab if (isinstance(np_lab, torch.Tensor) and np_lab.is_pinned()) else None
+    lab = np_lab.numpy() if isinstance(np_lab, torch.Tensor) else np_lab
+    if lab.ndim != 4 or lab.dtype.itemsize != 1:
+        raise ValueError('upload_label: the label must be a one-byte (C or P, D, H, W) array, got %s %s' % (lab.dtype, lab.shape))
+    C = int(num_classes)
+    if lab.shape[0] != C:
+        assert lab.shape[0] * 8 < C + 10 and lab.shape[0] * 8 >= C, 'packed channel count %d does not fit %d classes (:469)' % (lab.shape[0], C)
+        if lab.dtype != np.uint8:
+            raise ValueError('upload_label: a bit-packed label must be uint8, got %s' % lab.dtype)
+        pin = pinned                          # a DataLoader with pin_memory hands the bytes over page-locked already
+        if pin is None:
+            pin = torch.empty(lab.shape, dtype=torch.uint8).pin_memory()
+            np.copyto(pin.numpy(), lab)
+        return PackedBits(pin.to(device, non_blocking=True)[None], C)
+    lab = lab.view(np.uint8)
+    _, D, H, W = lab.shape
+    P, HW = (C + 7) // 8, H * W
+    n = slab_depth(C, D, H, W, chunk_bytes)
+    cur, cs = torch.cuda.current_stream(device), _copy_stream(device)
+    out = torch.empty((1, P, D, H, W), device=device, dtype=torch.uint8)
+    out.record_stream(cs)
+    cs.wait_stream(cur)                       # the allocator may hand out memory the current stream has not finished with
+    L = _l.lib()
+    pins = [torch.empty(C * n * HW, dtype=torch.uint8).pin_memory() for _ in range(2 if n < D else 1)]
+    events = [None] * len(pins)
+    with torch.cuda.device(device), torch.cuda.stream(cs):
+        devs = [torch.empty(C * n * HW, device=device, dtype=torch.uint8) for _ in pins]
+        for i, z0 in enumerate(range(0, D, n)):
+            k, m = i % len(pins), min(n, D - z0)
+            if events[k] is not None:
+                events[k].synchronize()       # the host is about to overwrite this staging buffer
+            np.copyto(pins[k][:C * m * HW].numpy().reshape(C, m, H, W), lab[:, z0:z0 + m])
+            devs[k][:C * m * HW].copy_(pins[k][:C * m * HW], non_blocking=True)
+            _l.check(L.rsuper_pack_bits(devs[k].data_ptr(), out.data_ptr() + z0 * HW, 1, C, m * HW, m * HW, D * HW, cs.cuda_stream), 'pack_bits')
+            events[k] = torch.cuda.Event()
+            events[k].record(cs)
+    cur.wait_stream(cs)
+    return PackedBits(out, C)
 
 
 _FORCE = {}      # (C, channels, device) -> (C,) uint8 device table of the channels PackedBits.planes always inflates

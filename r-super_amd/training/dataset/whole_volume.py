@@ -101,11 +101,12 @@ def random_crop(tensor_img, tensor_lab, d, h, w, scale, rotate, translate, pad=N
 
 
 def crop_annotated(tensor_img, tensor_lab, d, h, w, classes, lesion_classes, tumor_class_names, scale, rotate, translate, crop_on_tumor=True,
-                   pad=None):
+                   pad=None, counts=None):
     """The per-voxel-annotated branch of `crop()` (:837-851): random_crop_on_tumor always runs (and consumes its draws); with crop_on_tumor off its
     RESULT then goes through random_crop, as the reference's fall-through does.  The reference also swallows any exception of the first call and
     falls back to random_crop of the uncropped volume; here an error is an error and propagates."""
-    img, lab = random_crop_on_tumor(tensor_img, tensor_lab, d, h, w, classes, lesion_classes, tumor_class_names, scale, rotate, translate, pad=pad)
+    img, lab = random_crop_on_tumor(tensor_img, tensor_lab, d, h, w, classes, lesion_classes, tumor_class_names, scale, rotate, translate, pad=pad,
+                                    counts=counts)
     if not crop_on_tumor:
         img, lab = random_crop(img, lab, d, h, w, scale, rotate, translate)
     return img, lab
@@ -164,7 +165,7 @@ def report_sample(tensor_img, tensor_lab, report_rows, d, h, w, classes, classes
     """One report-annotated volume -> its training sample (`__getitem__` :489 and :523-527): crop_report, then assign_labels,
     estimate_tumor_volume and get_chosen_segment_mask.  The three volumes come from ONE label_remap launch on the cropped classes_ufo label: the
     chosen-segment table, written over the assigned label's classes, is composed with assign_labels' table.  -> {'image', 'label',
-    'unk_channels', 'mask' (PackedBits of `classes`), 'volumes' (10,), 'diameters' (10, 3), 'tumor_in_crop', 'unknown_per_voxel'}."""
+    'unk_channels', 'mask' (PackedBits of `classes`), 'volumes' (10,), 'diameters' (10, 3), 'tumor_in_crop', 'unknown_per_voxel', 'volumes_host' (estimate_tumor_volume's list, as save() writes it)}."""
     from .augmented import estimate_tumor_volume
     classes, classes_ufo = list(classes), list(classes_ufo)
     img, lab, selected = crop_report(tensor_img, tensor_lab, report_rows, d, h, w, classes_ufo, tumor_class_names, scale, rotate, translate, pad)
@@ -181,7 +182,7 @@ def report_sample(tensor_img, tensor_lab, report_rows, d, h, w, classes, classes
     label, unk_map, mask = augmentation.label_remap(lab, len(classes), [[ml, mu, mc]], [[ol, ou, 0]])
     return {'image': img, 'label': label, 'unk_channels': unk_map, 'mask': mask,
             'volumes': torch.tensor(volumes).float().to(img.device), 'diameters': diameters.float().to(img.device),
-            'tumor_in_crop': selected, 'unknown_per_voxel': unk}
+            'tumor_in_crop': selected, 'unknown_per_voxel': unk, 'volumes_host': list(volumes)}
 
 
 class DeviceCropper:
@@ -206,31 +207,37 @@ class DeviceCropper:
         self.device = torch.device(device)
         foreground_class_indices(self.tumor_class_names, self.classes)       # a name that is no class fails here, not in the first batch
 
-    def crop_one(self, image, packed_label, report_rows=None, report=False):
+    def crop_one(self, image, packed_label, report_rows=None, report=False, counts=None):
+        """One volume -> its crop.  image / packed_label may already be on the device (the whole-CT loader uploads them itself: packed_label is then a
+        (P, D, H, W) uint8 device tensor or a one-sample PackedBits).  counts: the LabelCounts of an annotated volume when the caller has them."""
         if report and self.classes_ufo is None:
             raise ValueError('DeviceCropper: a report-annotated volume needs classes_ufo')
         C = len(self.classes_ufo) if report else len(self.classes)
         img = torch.as_tensor(image)
-        lab = torch.as_tensor(packed_label)
+        lab = packed_label.packed[0] if isinstance(packed_label, PackedBits) else torch.as_tensor(packed_label)
         if img.dim() != 3 or img.dtype not in (torch.float32, torch.int16):
             raise ValueError('DeviceCropper: the image must be a float32 or int16 (D, H, W) volume, got %s %s' % (img.dtype, tuple(img.shape)))
         if lab.dim() != 4 or lab.dtype != torch.uint8 or tuple(lab.shape[1:]) != tuple(img.shape):
             raise ValueError('DeviceCropper: the label must be the uint8 (P, D, H, W) packbits array of the image grid')
         img = img.to(self.device, non_blocking=True)[None, None]
-        lab = PackedBits(lab.to(self.device, non_blocking=True)[None], C)
+        lab = packed_label if isinstance(packed_label, PackedBits) else PackedBits(lab.to(self.device, non_blocking=True)[None], C)
+        assert lab.C == C, 'the label has %d classes, expected %d' % (lab.C, C)
         d, h, w = self.training_size
         if report:
             return report_sample(img, lab, report_rows, d, h, w, self.classes, self.classes_ufo, self.tumor_class_names, self.scale, self.rotate,
                                  self.translate, pad=large_size(d, h, w))
         return crop_annotated(img, lab, d, h, w, self.classes, self.lesion_classes, self.tumor_class_names, self.scale, self.rotate, self.translate,
-                              crop_on_tumor=self.crop_on_tumor, pad=large_size(d, h, w))
+                              crop_on_tumor=self.crop_on_tumor, pad=large_size(d, h, w), counts=counts)
 
     def __call__(self, volumes):
         if not volumes:
             raise ValueError('DeviceCropper: an empty batch')
-        crops = [self.crop_one(*v, report=True) if len(v) == 3 else self.crop_one(*v) for v in volumes]
+        return self.assemble([self.crop_one(*v, report=True) if len(v) == 3 else self.crop_one(*v) for v in volumes])
+
+    def assemble(self, crops):
+        """The crops of crop_one (pairs of annotated volumes, dictionaries of report volumes) -> the batch dictionary."""
         C, B = len(self.classes), len(crops)
-        self.last_meta = [{k: c[k] for k in ('tumor_in_crop', 'unknown_per_voxel')} if isinstance(c, dict) else None for c in crops]
+        self.last_meta = [{k: c[k] for k in ('tumor_in_crop', 'unknown_per_voxel', 'volumes_host') if k in c} if isinstance(c, dict) else None for c in crops]
         image = torch.cat([c['image'] if isinstance(c, dict) else c[0] for c in crops], 0)
         label = torch.cat([c['label'].packed if isinstance(c, dict) else c[1].packed for c in crops], 0)
         batch = {'image': image,
