@@ -532,6 +532,28 @@ long rsuper_largest_component_workspace_bytes(int D, int H, int W);
 int rsuper_largest_component(const void* mask, int is_u8, int D, int H, int W, uint8_t* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Report-guided pseudo-label refinement -- baselines/pseudo_labels/pseudo_label_report_refinement.py extract_lesion_candidates :48-70, for `planes`
+ * lesion planes [planes][D][H][W] at once, each with its own lesion count.  One iteration of a plane: peak = max(work) at its first C-order voxel;
+ * stop when peak < min_peak or kept == n_lesions; thr = peak_cut * peak (one f32 multiply); the 26-connected component of work >= thr that holds the
+ * peak voxel is zeroed in work and, when it has at least min_voxels voxels, set to 1 in out and counted in kept.
+ * state: planes * RSUPER_LESION_STATE_WORDS 32-bit words on the device (8-byte aligned), per plane
+ *   { int kept, iterations, done, n_lesions; u64 peak key; u32 seed root, seed component size }.
+ * _begin zeroes out and the state (no memset) and stores the counts (host array; n <= 0: done at once).  _run enqueues `iterations` iterations; every
+ * kernel returns at once for a plane whose `done` word is set, so iterations past the end leave work, out and the state as they are: enqueue a batch,
+ * read the state, repeat while a plane has neither `done` nor kept == n_lesions.  A plane that is not done zeroes at least one positive voxel per
+ * iteration, so the loop ends after at most D*H*W iterations.  work is consumed in place.  workspace: _workspace_bytes on the device, any content.
+ * RS_ERR_ARG: null pointers, planes outside 1..RSUPER_LESION_MAX_PLANES, D*H*W > 2^31, !(0 < peak_cut <= 1), !(min_peak > 0), min_voxels < 1,
+ * iterations < 1.  Non-finite values in work are the caller's error and the result is then unspecified, but nothing is read out of bounds and every
+ * plane ends: the stop test is !(peak >= min_peak), so a plane whose peak is NaN gets `done` at once; a NaN with the sign bit set orders below every
+ * value and never enters a mask; +inf is a peak like any other. */
+#define RSUPER_LESION_MAX_PLANES 64
+#define RSUPER_LESION_STATE_WORDS 8
+long rsuper_lesion_candidates_workspace_bytes(int planes, int D, int H, int W);
+int rsuper_lesion_candidates_begin(uint8_t* out, int planes, int D, int H, int W, const int* n_lesions, void* state, void* stream);
+int rsuper_lesion_candidates_run(float* work, uint8_t* out, int planes, int D, int H, int W, float peak_cut, int min_voxels, float min_peak, void* state,
+                                 void* workspace, int iterations, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Validation metrics -- metric/metrics.py compute_surface_distances :265-573.  Masks of up to 2^31 corners ((D+1) * (H+1) * (W+1)).
  * No call issues a memset: counters and bounds are initialised by the call's own kernels.
  * ------------------------------------------------------------------------------------------------ */

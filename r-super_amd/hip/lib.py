@@ -131,6 +131,9 @@ _SIGS = {
     'rsuper_organ_mask_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     'rsuper_largest_component_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_largest_component': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    'rsuper_lesion_candidates_workspace_bytes': (c_long, [c_int] * 4),
+    'rsuper_lesion_candidates_begin': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    'rsuper_lesion_candidates_run': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, c_int, c_float, P, P, c_int, P]),
     'rsuper_affine_crop': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),
     'rsuper_intensity_augment_workspace_bytes': (c_long, [c_int] * 4),
     'rsuper_intensity_augment_launches': (c_int, [c_int, P]),

@@ -38,6 +38,8 @@ whole-CT label upload (training/dataset/packed.py; no derivative):
 whole-case preprocessing and resampling (inference/preprocess.py, inference/resample.py; no derivative):
     torch.ops.rsuper.ct_normalize(hu, lo, hi, out_shape, offset, workspace) -> (z-scored, zero-padded volume, (mean, std))
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
+report-guided pseudo-label refinement (baselines/pseudo_labels/pseudo_label_report_refinement.py; no derivative):
+    torch.ops.rsuper.lesion_candidates(prob, n_lesions, peak_cut, min_voxels, min_peak, batch) -> (uint8 masks, per-plane state words)
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -301,3 +303,16 @@ def install_metric_ops(surface_distances, edt3):
             _register_plain('edt3', '(Tensor codes, int[] box, float[] spacing, Tensor? workspace=None) -> Tensor', edt3),
         )
     return _METRIC_OPS
+
+
+_PSEUDO_LABEL_OP = None
+
+
+def install_pseudo_label_ops(lesion_candidates):
+    """Register the lesion-candidate extraction of baselines/pseudo_labels (at the end of that module; idempotent) as a plain CUDA kernel: masks and
+    counters have no derivative."""
+    global _PSEUDO_LABEL_OP
+    if _PSEUDO_LABEL_OP is None:
+        _PSEUDO_LABEL_OP = _register_plain('lesion_candidates', '(Tensor prob, int[] n_lesions, float peak_cut, int min_voxels, float min_peak, int batch) '
+                                           '-> (Tensor mask, Tensor state)', lesion_candidates)
+    return _PSEUDO_LABEL_OP
