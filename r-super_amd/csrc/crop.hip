@@ -3,16 +3,13 @@
 // on a whole-CT plane to pick one voxel; here presence and counts are popcounts over the packed bytes, the chosen voxel is "the k-th set bit of column
 // c in row-major order", and the crop is a box copy of the image and of the packed byte planes.
 //
-// class_counts   packed [B][P][V] u8 (np.packbits(axis = class): class c is bit 7 - (c & 7) of byte plane c >> 3).  The V voxels of a sample are cut
-//                into chunks of RSUPER_CROP_CHUNK = 16384 voxels.  Block (chunk, b) writes ONE row of the chunk table [B][chunks][C + 1] int32: the set
-//                voxels of every class and, in column C, the voxels whose P bytes are all zero (label.sum(0) == 0: packbits zero-fills the padding
-//                bits).  A lane reads 16 voxels of a plane as one 16-byte vector, from the first 16-byte boundary of the chunk in plane 0 on; the fewer
-//                than 16 voxels before it and after the last whole vector go to 32 lanes of the same block as single bytes (a chunk's row must hold
-//                exactly its own voxels, so every block owns its head and tail).  A plane whose base is shifted against plane 0 (V % 16 != 0) is read
-//                with unaligned 16-byte loads.  Counting: __popc of the dword under the class's bit replicated into its 4 bytes; the OR of the planes
-//                stays in registers for the background column.  A second launch sums the rows into [B][C + 1] int64.  Every entry is written, nothing
-//                is accumulated in memory: no memset, no atomics, the same bits on every run.  plain: the label is [B][C][V] bytes, class c = plane c,
-//                a voxel is set where its byte is not zero (the u8 / int64 labels of the reference's own functions); same table.
+// class_counts   packed [B][P][V] u8, read chunk by chunk (layout, chunks, head and tail: label_bits.hpp).  Block (chunk, b) writes ONE row of the chunk
+//                table [B][chunks][C + 1] int32: the set voxels of every class and, in column C, the voxels whose P bytes are all zero
+//                (label.sum(0) == 0: packbits zero-fills the padding bits).  Counting: __popc of the dword under the class's bit replicated into its
+//                4 bytes; the OR of the planes stays in registers for the background column.  A second launch sums the rows into [B][C + 1] int64.
+//                Every entry is written, nothing is accumulated in memory: no memset, no atomics, the same bits on every run.  plain: the label is
+//                [B][C][V] bytes, class c = plane c, a voxel is set where its byte is not zero (the u8 / int64 labels of the reference's own
+//                functions); same table.
 // select_voxel   one block.  Prefix sums of column c over the table find the chunk that holds rank k; inside it every lane builds the 64-bit mask of
 //                its 64 consecutive voxels, the popcounts are prefix-summed over the lanes, and the lane that holds the rank clears that many low bits.
 //                Lanes own consecutive voxels, so the order is row-major: (z, y, x) = torch.nonzero(mask)[k].  Reads stay inside the chunk whatever
@@ -24,31 +21,17 @@
 //                used is written to origin_out.  One lane = 4 consecutive voxels along w: one 16-byte store per image channel and one dword per byte
 //                plane when w % 4 == 0, voxel by voxel otherwise; 4 source voxels inside one row are one (possibly unaligned) load.
 #include "common.hpp"
-#include "../../include/rsuper_hip.h"
+#include "label_bits.hpp"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int CHUNK = RSUPER_CROP_CHUNK;
-constexpr int VPL = CHUNK / 16 / NT;                    // 16-byte vectors of a plane per lane: 4
+constexpr int NT = LB_NT;
+constexpr int CHUNK = LB_CHUNK;
 constexpr int LPV = CHUNK / NT;                          // voxels per lane of the selection: 64
 constexpr int CP = RSUPER_CROP_MAX_CLASSES / 8;          // bit-packed byte planes the counting kernel takes
 constexpr int MAXV = RSUPER_AFFINE_MAX_VOLUMES, MAXPL = RSUPER_AFFINE_MAX_PLANES, MAXB = 8;
-static_assert(VPL * 16 * NT == CHUNK && LPV == 64, "a lane of the selection owns one 64-bit mask");
+static_assert(LPV == 64, "a lane of the selection owns one 64-bit mask");
 static_assert(RSUPER_CROP_MAX_CLASSES + 1 <= NT, "one lane per column of a table row");
-
-__device__ __forceinline__ uint4 ld16(const uint8_t* p, bool aligned) {
-    if (aligned) return *reinterpret_cast<const uint4*>(p);
-    uint4 q;
-    __builtin_memcpy(&q, p, 16);
-    return q;
-}
-
-// bit 0 of every byte = that byte is not zero
-__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w) {
-    w |= w >> 4; w |= w >> 2; w |= w >> 1;
-    return w & 0x01010101u;
-}
 
 struct CountArgs {
     const uint8_t* packed;                               // [B][P][V]
@@ -61,52 +44,32 @@ __global__ __launch_bounds__(NT) void class_counts_kernel(CountArgs a) {
     __shared__ int sh[RSUPER_CROP_MAX_CLASSES][NT / 64];
     __shared__ int shnz[NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long start = (long)blockIdx.x * CHUNK;
-    const int len = a.V - start < CHUNK ? (int)(a.V - start) : CHUNK;
-    const uint8_t* __restrict__ base = a.packed + (long)blockIdx.y * a.P * a.V + start;
-    int h = (int)((16 - (uintptr_t)base % 16) % 16);
-    if (h > len) h = len;
-    const int nvec = (len - h) / 16, tail0 = h + nvec * 16;
-    // the lane's single byte: lanes 0..15 the head, lanes 16..31 the tail
-    const int soff = tid < h ? tid : (tid >= 16 && tail0 + tid - 16 < len && tid < 32) ? tail0 + tid - 16 : -1;
+    const LabelChunk ck(a.packed + (long)blockIdx.y * a.P * a.V, a.V, blockIdx.x, tid);
 
-    uint4 any[VPL];
+    uint4 any[LB_VPL];
     uint32_t anys = 0;
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) any[v] = make_uint4(0, 0, 0, 0);
+    for (int v = 0; v < LB_VPL; ++v) any[v] = make_uint4(0, 0, 0, 0);
 
     for (int p = 0; p < a.P; ++p) {
-        const uint8_t* __restrict__ s = base + (long)p * a.V;
-        const bool aligned = (uintptr_t)(s + h) % 16 == 0;
         int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         auto take = [&](uint32_t w) {
             if (a.plain) acc[0] += __popc(nonzero_bytes(w));
             else
 #pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] += __popc(w & (0x80808080u >> j));
+                for (int j = 0; j < 8; ++j) acc[j] += __popc(w & (0x01010101u << class_bit(j)));
         };
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) {
-            const int g = v * NT + tid;
-            if (g < nvec) {
-                const uint4 q = ld16(s + h + 16 * g, aligned);
+        ck.for_each(p,
+            [&](int v, const uint4 q) {
                 any[v].x |= q.x; any[v].y |= q.y; any[v].z |= q.z; any[v].w |= q.w;
                 take(q.x); take(q.y); take(q.z); take(q.w);
-            }
-        }
-        if (soff >= 0) {
-            const uint32_t w = s[soff];
-            anys |= w;
-            take(w);
-        }
-        // a lane holds at most 16 * VPL + 1 voxels and a wave 64 times that: two counts share a dword through the wave reduction
+            },
+            [&](uint32_t w) { anys |= w; take(w); });
+        // a lane holds at most 16 * LB_VPL + 1 voxels and a wave 64 times that: two counts share a dword through the wave reduction
         uint32_t pk[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            pk[i] = (uint32_t)acc[2 * i] | (uint32_t)acc[2 * i + 1] << 16;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) pk[i] += __shfl_xor(pk[i], o, 64);
-        }
+        for (int i = 0; i < 4; ++i) pk[i] = (uint32_t)acc[2 * i] | (uint32_t)acc[2 * i + 1] << 16;
+        wave_reduce_all<RedSum, RedSum, RedSum, RedSum>(pk[0], pk[1], pk[2], pk[3]);
         if (lane == 0) {
             if (a.plain) sh[p][wave] = (int)(pk[0] & 0xffffu);
             else
@@ -116,24 +79,13 @@ __global__ __launch_bounds__(NT) void class_counts_kernel(CountArgs a) {
     }
     int nz = __popc(nonzero_bytes(anys));
 #pragma unroll
-    for (int v = 0; v < VPL; ++v)
+    for (int v = 0; v < LB_VPL; ++v)
         nz += __popc(nonzero_bytes(any[v].x)) + __popc(nonzero_bytes(any[v].y)) + __popc(nonzero_bytes(any[v].z)) + __popc(nonzero_bytes(any[v].w));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nz += __shfl_xor(nz, o, 64);
-    if (lane == 0) shnz[wave] = nz;
+    block_stage<RedSum>(nz, shnz);
     __syncthreads();
     int* __restrict__ row = a.table + ((long)blockIdx.y * a.nchunks + blockIdx.x) * (a.C + 1);
-    if (tid < a.C) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < NT / 64; ++w) s += sh[tid][w];
-        row[tid] = s;
-    } else if (tid == a.C) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < NT / 64; ++w) s += shnz[w];
-        row[tid] = len - s;
-    }
+    if (tid < a.C) row[tid] = block_finish<RedSum>(sh[tid]);
+    else if (tid == a.C) row[tid] = ck.len - block_finish<RedSum>(shnz);
 }
 
 // block (column, b): the column's sum over the chunk rows
@@ -143,14 +95,9 @@ __global__ __launch_bounds__(NT) void class_totals_kernel(const int* __restrict_
     const int* __restrict__ t = table + (long)b * nchunks * cols + col;
     long long s = 0;
     for (int j = tid; j < nchunks; j += NT) s += t[(long)j * cols];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((tid & 63) == 0) shw[tid >> 6] = s;
+    block_stage<RedSum>(s, shw);
     __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < NT / 64; ++w) s += shw[w];
-        totals[(long)b * cols + col] = s;
-    }
+    if (tid == 0) totals[(long)b * cols + col] = block_finish<RedSum>(shw);
 }
 
 struct SelArgs {
@@ -198,7 +145,7 @@ __global__ __launch_bounds__(NT) void select_voxel_kernel(SelArgs a) {
     unsigned long long mask = 0;
     const bool background = a.col == a.C;
     const int p0 = background ? 0 : a.plain ? a.col : a.col >> 3, p1 = background ? a.P : p0 + 1;
-    const int shift = 7 - (a.col & 7);
+    const int shift = class_bit(a.col);
     for (int q = 0; q < LPV / 16; ++q) {
         if (q * 16 >= nvalid) break;
         uint32_t f[4] = {0, 0, 0, 0};                    // bit 0 of byte i = voxel 4 * word + i has a bit in the column's planes
@@ -217,7 +164,7 @@ __global__ __launch_bounds__(NT) void select_voxel_kernel(SelArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint32_t sel = background ? f[i] ^ 0x01010101u : f[i];
-            mask |= (unsigned long long)((sel * 0x01020408u) >> 24 & 0xfu) << (q * 16 + i * 4);   // bytes' bit 0 -> 4 adjacent bits
+            mask |= (unsigned long long)fold_nibble(sel) << (q * 16 + i * 4);
         }
     }
     if (nvalid < LPV) mask &= (1ull << nvalid) - 1ull;   // voxels past the volume's end are nobody's

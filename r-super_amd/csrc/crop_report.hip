@@ -3,10 +3,9 @@
 // inflates the label, sums the chosen segment planes, calls torch.nonzero for six minima / maxima, runs scipy's erosions / dilations over the whole CT
 // and stacks three more inflated volumes plane by plane.  Here:
 //
-// union_bbox     packed [B][P][V] u8 (the layout of class_counts, crop.hip; plain: [B][C][V] bytes) and one HOST 64-bit class set per sample.  A voxel
-//                is on where any class of the set is.  Block (chunk, b) reads its RSUPER_CROP_CHUNK voxels of the planes the set touches (16 voxels per
-//                16-byte vector, head and tail as single bytes, as class_counts does) and writes ONE row (count, min z y x, max z y x) of the partial
-//                table; one div / mod pair per non-empty vector.  A second launch folds the rows in a fixed order into count [B] int64 and bbox [B][6]
+// union_bbox     packed [B][P][V] u8 (layout and chunks: label_bits.hpp; plain: [B][C][V] bytes) and one HOST 64-bit class set per sample.  A voxel
+//                is on where any class of the set is.  Block (chunk, b) reads its chunk of the planes the set touches and writes ONE row (count,
+//                min z y x, max z y x) of the partial table; one div / mod pair per non-empty vector.  A second launch folds the rows in a fixed order into count [B] int64 and bbox [B][6]
 //                int32.  No voxel -> min = (D, H, W), max = (-1, -1, -1).
 // union_bits     the same union inside the sub-box (z0, y0, x0) + (nz, ny, nx) of sample b as bits [nz][ny][ceil(nx / 64)] u64: one wave per word, one
 //                voxel per lane, one __ballot.  Bits past nx are zero.
@@ -20,37 +19,17 @@
 //
 // No hipMemsetAsync, no atomics; every output and workspace entry a later launch reads is written by an earlier launch of the same call.
 #include "common.hpp"
-#include "../../include/rsuper_hip.h"
+#include "label_bits.hpp"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int CHUNK = RSUPER_CROP_CHUNK;
-constexpr int VPL = CHUNK / 16 / NT;
+constexpr int NT = LB_NT;
+constexpr int CHUNK = LB_CHUNK;
 constexpr int CP = RSUPER_CROP_MAX_CLASSES / 8;
 constexpr int MAXB = 8, MAXV = 3, ROW = 8;               // samples per launch, remapped volumes, ints of a partial row
 constexpr int TW = RSUPER_REMAP_TABLE_WORDS;
 constexpr int BIG = 0x7fffffff;
 typedef unsigned long long u64;
-
-__device__ __forceinline__ uint4 ld16(const uint8_t* p, bool aligned) {
-    if (aligned) return *reinterpret_cast<const uint4*>(p);
-    uint4 q;
-    __builtin_memcpy(&q, p, 16);
-    return q;
-}
-
-// bit i = byte i of w is not zero
-__device__ __forceinline__ uint32_t nonzero_nibble(uint32_t w) {
-    w |= w >> 4; w |= w >> 2; w |= w >> 1;
-    return ((w & 0x01010101u) * 0x01020408u) >> 24 & 0xfu;
-}
-
-// the byte of plane p under which the classes of `set` sit (plain: all of it or nothing)
-__device__ __forceinline__ uint32_t plane_mask(u64 set, int p, int plain) {
-    if (plain) return (set >> p) & 1ull ? 0xffu : 0u;
-    return __brev((uint32_t)(set >> (8 * p)) & 0xffu) >> 24;
-}
 
 struct Box {
     int cnt, mn[3], mx[3];
@@ -65,26 +44,14 @@ struct Box {
 // the block's box -> row[0..6] (count, min z y x, max z y x); every thread of the block calls it
 __device__ void block_box(Box v, int* __restrict__ row) {
     __shared__ int sh[7][NT / 64];
-    int f[7] = {v.cnt, v.mn[0], v.mn[1], v.mn[2], v.mx[0], v.mx[1], v.mx[2]};
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        f[0] += __shfl_xor(f[0], o, 64);
-#pragma unroll
-        for (int i = 1; i < 4; ++i) f[i] = min(f[i], __shfl_xor(f[i], o, 64));
-#pragma unroll
-        for (int i = 4; i < 7; ++i) f[i] = max(f[i], __shfl_xor(f[i], o, 64));
-    }
     const int tid = threadIdx.x;
+    int f[7] = {v.cnt, v.mn[0], v.mn[1], v.mn[2], v.mx[0], v.mx[1], v.mx[2]};
+    wave_reduce_all<RedSum, RedMin, RedMin, RedMin, RedMax, RedMax, RedMax>(f[0], f[1], f[2], f[3], f[4], f[5], f[6]);
     if ((tid & 63) == 0)
 #pragma unroll
         for (int i = 0; i < 7; ++i) sh[i][tid >> 6] = f[i];
     __syncthreads();
-    if (tid < 7) {
-        int s = sh[tid][0];
-#pragma unroll
-        for (int w = 1; w < NT / 64; ++w) s = tid == 0 ? s + sh[tid][w] : tid < 4 ? min(s, sh[tid][w]) : max(s, sh[tid][w]);
-        row[tid] = s;
-    }
+    if (tid < 7) row[tid] = tid == 0 ? block_finish<RedSum>(sh[0]) : tid < 4 ? block_finish<RedMin>(sh[tid]) : block_finish<RedMax>(sh[tid]);
 }
 
 struct UnionArgs {
@@ -97,44 +64,31 @@ struct UnionArgs {
 
 __global__ __launch_bounds__(NT) void union_bbox_kernel(UnionArgs a) {
     const int tid = threadIdx.x, b = blockIdx.y;
-    const long start = (long)blockIdx.x * CHUNK;
-    const int len = a.V - start < CHUNK ? (int)(a.V - start) : CHUNK;
-    const uint8_t* __restrict__ base = a.packed + (long)b * a.P * a.V + start;
-    int h = (int)((16 - (uintptr_t)base % 16) % 16);
-    if (h > len) h = len;
-    const int nvec = (len - h) / 16, tail0 = h + nvec * 16;
-    const int soff = tid < h ? tid : (tid >= 16 && tid < 32 && tail0 + tid - 16 < len) ? tail0 + tid - 16 : -1;
+    const LabelChunk ck(a.packed + (long)b * a.P * a.V, a.V, blockIdx.x, tid);
     const u64 set = a.set[b];
 
-    uint4 any[VPL];
+    uint4 any[LB_VPL];
     uint32_t anys = 0;
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) any[v] = make_uint4(0, 0, 0, 0);
+    for (int v = 0; v < LB_VPL; ++v) any[v] = make_uint4(0, 0, 0, 0);
     for (int p = 0; p < a.P; ++p) {
         const uint32_t bm = plane_mask(set, p, a.plain);
         if (!bm) continue;                               // the same in every lane: a plane the set does not touch is not read
         const uint32_t rep = bm * 0x01010101u;
-        const uint8_t* __restrict__ s = base + (long)p * a.V;
-        const bool aligned = (uintptr_t)(s + h) % 16 == 0;
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) {
-            const int g = v * NT + tid;
-            if (g < nvec) {
-                const uint4 q = ld16(s + h + 16 * g, aligned);
-                any[v].x |= q.x & rep; any[v].y |= q.y & rep; any[v].z |= q.z & rep; any[v].w |= q.w & rep;
-            }
-        }
-        if (soff >= 0) anys |= s[soff] & bm;
+        ck.for_each(p,
+            [&](int v, const uint4 q) { any[v].x |= q.x & rep; any[v].y |= q.y & rep; any[v].z |= q.z & rep; any[v].w |= q.w & rep; },
+            [&](uint32_t w) { anys |= w & bm; });
     }
 
     Box box;
     box.init();
     const uint32_t HW = (uint32_t)a.H * (uint32_t)a.W, W = (uint32_t)a.W;
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-        const uint32_t m = nonzero_nibble(any[v].x) | nonzero_nibble(any[v].y) << 4 | nonzero_nibble(any[v].z) << 8 | nonzero_nibble(any[v].w) << 12;
+    for (int v = 0; v < LB_VPL; ++v) {
+        const uint32_t m = fold_nibble(nonzero_bytes(any[v].x)) | fold_nibble(nonzero_bytes(any[v].y)) << 4 | fold_nibble(nonzero_bytes(any[v].z)) << 8 |
+                           fold_nibble(nonzero_bytes(any[v].w)) << 12;
         if (!m) continue;
-        const uint32_t lin = (uint32_t)(start + h + 16 * (v * NT + tid));      // V < 2^31
+        const uint32_t lin = (uint32_t)(ck.start + ck.vec_off(v));             // V < 2^31
         const uint32_t z = lin / HW, r = lin - z * HW, y = r / W, x = r - y * W;
         const int lo = __ffs((int)m) - 1, hi = 31 - __clz((int)m);
         box.cnt += __popc(m);
@@ -146,8 +100,8 @@ __global__ __launch_bounds__(NT) void union_bbox_kernel(UnionArgs a) {
                     box.add((int)zz, (int)yy, (int)xx, (int)xx);
                 }
     }
-    if (soff >= 0 && anys) {
-        const uint32_t l = (uint32_t)(start + soff), zz = l / HW, rr = l - zz * HW, yy = rr / W, xx = rr - yy * W;
+    if (ck.soff >= 0 && anys) {
+        const uint32_t l = (uint32_t)(ck.start + ck.soff), zz = l / HW, rr = l - zz * HW, yy = rr / W, xx = rr - yy * W;
         box.cnt += 1;
         box.add((int)zz, (int)yy, (int)xx, (int)xx);
     }
@@ -170,12 +124,7 @@ __global__ __launch_bounds__(NT) void fold_box_kernel(const int* __restrict__ pa
 #pragma unroll
         for (int i = 0; i < 3; ++i) { f[i] = min(f[i], row[1 + i]); f[3 + i] = max(f[3 + i], row[4 + i]); }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        c += __shfl_xor(c, o, 64);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { f[i] = min(f[i], __shfl_xor(f[i], o, 64)); f[3 + i] = max(f[3 + i], __shfl_xor(f[3 + i], o, 64)); }
-    }
+    wave_reduce_all<RedSum, RedMin, RedMin, RedMin, RedMax, RedMax, RedMax>(c, f[0], f[1], f[2], f[3], f[4], f[5]);
     if ((tid & 63) == 0) {
         shc[tid >> 6] = c;
 #pragma unroll
@@ -183,17 +132,13 @@ __global__ __launch_bounds__(NT) void fold_box_kernel(const int* __restrict__ pa
     }
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < NT / 64; ++w) {
-            c += shc[w];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { f[i] = min(f[i], shb[i][w]); f[3 + i] = max(f[3 + i], shb[3 + i][w]); }
-        }
+        c = block_finish<RedSum>(shc);
         const int e[3] = {ez, ey, ex}, ad[3] = {az, ay, ax};
         count[b] = c;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            bbox[b * 6 + i] = (c ? f[i] : e[i]) + ad[i];
-            bbox[b * 6 + 3 + i] = (c ? f[3 + i] : -1) + ad[i];
+            bbox[b * 6 + i] = (c ? block_finish<RedMin>(shb[i]) : e[i]) + ad[i];
+            bbox[b * 6 + 3 + i] = (c ? block_finish<RedMax>(shb[3 + i]) : -1) + ad[i];
         }
     }
 }
@@ -339,7 +284,7 @@ __global__ __launch_bounds__(NT) void label_remap_kernel(RemapArgs a) {
                 const u64 mk = shm[k * a.C_out + c];
                 const uint32_t one = (uint32_t)(ones >> c & 1ull);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) w |= (((bits[i] & mk) != 0ull ? 1u : 0u) | one) << (8 * i + 7 - j);
+                for (int i = 0; i < 4; ++i) w |= (((bits[i] & mk) != 0ull ? 1u : 0u) | one) << (8 * i + 7 - j);   // class_bit(c): j = c & 7
             }
             uint8_t* __restrict__ q = a.out[k] + ((long)b * a.P_out + p) * a.v + v0;
             if (a.vec) *reinterpret_cast<uint32_t*>(q) = w;

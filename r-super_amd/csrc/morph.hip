@@ -745,211 +745,6 @@ int rs_launch_rank_assign(const long long* ids, unsigned int n, float dlog2, flo
     return rs_check_launch();
 }
 
-// Bit-packed label ingestion.  The reference stores label / unk / chosen-segment volumes as
-// np.packbits(bool (C, D, H, W), axis=0) (dataset_abdomenatlas_UFO.py:955,970,975) and inflates them on the host with
-// np.unpackbits(...)[:C] (:1031-1034) before a 16x larger H2D copy.  Here the packed bytes travel and are inflated on the
-// device: out[b][c][v] = (packed[b][c >> 3][v] >> (7 - (c & 7))) & 1   (packbits is MSB-first).
-// Thread = 16 voxels of one byte plane: one 16-byte load, up to eight 16-byte stores.
-__global__ __launch_bounds__(256) void unpack_bits_kernel(const uint8_t* __restrict__ packed, uint8_t* __restrict__ out, int P, int C, long V) {
-    const long nvec = (V + 15) / 16;
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= nvec) return;
-    const int pl = blockIdx.y % P, b = blockIdx.y / P;
-    const uint8_t* src = packed + ((size_t)b * P + pl) * V;
-    const long v0 = t * 16;
-    const bool full = v0 + 16 <= V && (V & 15) == 0;
-    uint8_t in[16];
-    if (full) *(uint4*)in = *(const uint4*)(src + v0);
-    else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) in[j] = v0 + j < V ? src[v0 + j] : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int c = pl * 8 + k;
-        if (c >= C) break;
-        uint8_t o[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[j] = (in[j] >> (7 - k)) & 1;
-        uint8_t* dst = out + ((size_t)b * C + c) * V + v0;
-        if (full) *(uint4*)dst = *(const uint4*)o;
-        else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) if (v0 + j < V) dst[j] = o[j];
-        }
-    }
-}
-
-int rs_launch_unpack_bits(const uint8_t* packed, uint8_t* out, int B, int P, int C, long V, hipStream_t st) {
-    const long nvec = (V + 15) / 16;
-    hipLaunchKernelGGL(unpack_bits_kernel, dim3((unsigned)((nvec + 255) / 256), (unsigned)(B * P)), dim3(256), 0, st, packed, out, P, C, V);
-    return rs_check_launch();
-}
-
-// The inverse, np.packbits((src != 0), axis = class) on the device: dst[b][p][v] = OR_k (src[b][8 p + k][v] != 0) << (7 - k), classes >= C contribute 0.
-// What the dataset converter writes is the unpacked int8 (C, D, H, W) volume (dataset_conversion/nii2npz.py:80-82); the croppers read the packed form.
-// The two plane strides (bytes, >= V) let a z-slab held in a staging buffer be packed straight into its place of the whole packed volume.
-// nz4: per byte of a dword, 1 when the byte is non-zero (bit 7 of ((x & 0x7f..) + 0x7f..) | x is set exactly then; no carry leaves a byte).
-__device__ __forceinline__ uint32_t nz4(uint32_t x) { return ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) >> 7) & 0x01010101u; }
-
-// VEC: every plane of src and dst starts 16-byte aligned (bases and strides are multiples of 16).  Thread = 16 voxels of one byte plane: up to eight 16-byte
-// loads, one 16-byte store; the V % 16 tail of a plane goes byte by byte and nothing is read or written at or past V.
-// !VEC (an unaligned base or stride): thread = 1 voxel, up to eight byte loads (lanes read consecutive bytes), one byte store.
-template <bool VEC>
-__global__ __launch_bounds__(256) void pack_bits_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int P, int C, long V, long sstride, long dstride) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const int pl = blockIdx.y % P, b = blockIdx.y / P;
-    const int nk = min(8, C - pl * 8);                             // wave-uniform
-    const uint8_t* s = src + ((size_t)b * C + (size_t)pl * 8) * (size_t)sstride;
-    uint8_t* d = dst + ((size_t)b * P + pl) * (size_t)dstride;
-    if (VEC) {
-        const long v0 = t * 16;
-        if (v0 >= V) return;
-        if (v0 + 16 <= V) {
-            uint4 o = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (k < nk) {
-                    const uint4 x = *(const uint4*)(s + (size_t)k * (size_t)sstride + v0);
-                    o.x |= nz4(x.x) << (7 - k); o.y |= nz4(x.y) << (7 - k); o.z |= nz4(x.z) << (7 - k); o.w |= nz4(x.w) << (7 - k);
-                }
-            }
-            *(uint4*)(d + v0) = o;
-        } else {
-            for (long v = v0; v < V; ++v) {
-                unsigned o = 0;
-                for (int k = 0; k < nk; ++k) o |= (unsigned)(s[(size_t)k * (size_t)sstride + v] != 0) << (7 - k);
-                d[v] = (uint8_t)o;
-            }
-        }
-    } else {
-        if (t >= V) return;
-        unsigned o = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (k < nk) o |= (unsigned)(s[(size_t)k * (size_t)sstride + t] != 0) << (7 - k);
-        d[t] = (uint8_t)o;
-    }
-}
-
-int rs_launch_pack_bits(const uint8_t* src, uint8_t* dst, int B, int C, long V, long sstride, long dstride, hipStream_t st) {
-    const int P = (C + 7) / 8;
-    const bool vec = !(((uintptr_t)src | (uintptr_t)dst | (uintptr_t)sstride | (uintptr_t)dstride) & 15);
-    const long nthr = vec ? (V + 15) / 16 : V;
-    const dim3 grid((unsigned)((nthr + 255) / 256), (unsigned)(B * P));
-    if (vec) hipLaunchKernelGGL(pack_bits_kernel<true>, grid, dim3(256), 0, st, src, dst, P, C, V, sstride, dstride);
-    else hipLaunchKernelGGL(pack_bits_kernel<false>, grid, dim3(256), 0, st, src, dst, P, C, V, sstride, dstride);
-    return rs_check_launch();
-}
-
-__global__ void plane_flags_zero_kernel(uint8_t* flags, long planes);
-
-// The same inflation for SOME class planes only: plane (b, c) is written iff flags[b * C + c] != 0 or force[c] != 0 (either table may be null; both null = every
-// plane).  A byte plane none of whose eight classes is wanted is not read.  What the report losses need of a bit-packed volume: the lesion channels (force) and,
-// of the unknown map, the planes that hold a voxel at all (flags from plane_any_bits_kernel) -- the other planes of `out` are never written and never read.
-__global__ __launch_bounds__(256) void unpack_bits_sel_kernel(const uint8_t* __restrict__ packed, uint8_t* __restrict__ out, int P, int C, long V,
-                                                              const uint8_t* __restrict__ flags, const uint8_t* __restrict__ force) {
-    const long nvec = (V + 15) / 16;
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const int pl = blockIdx.y % P, b = blockIdx.y / P;
-    unsigned want = 0;                                           // wave-uniform (depends on the block's plane only)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int c = pl * 8 + k;
-        if (c < C && ((flags && flags[(size_t)b * C + c]) || (force && force[c]) || (!flags && !force))) want |= 1u << k;
-    }
-    if (!want || t >= nvec) return;
-    const uint8_t* src = packed + ((size_t)b * P + pl) * V;
-    const long v0 = t * 16;
-    const bool full = v0 + 16 <= V && (V & 15) == 0;
-    uint8_t in[16];
-    if (full) *(uint4*)in = *(const uint4*)(src + v0);
-    else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) in[j] = v0 + j < V ? src[v0 + j] : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (!((want >> k) & 1u)) continue;
-        const int c = pl * 8 + k;
-        uint8_t o[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) o[j] = (in[j] >> (7 - k)) & 1;
-        uint8_t* dst = out + ((size_t)b * C + c) * V + v0;
-        if (full) *(uint4*)dst = *(const uint4*)o;
-        else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) if (v0 + j < V) dst[j] = o[j];
-        }
-    }
-}
-int rs_launch_unpack_bits_sel(const uint8_t* packed, uint8_t* out, int B, int P, int C, long V, const uint8_t* flags, const uint8_t* force, hipStream_t st) {
-    const long nvec = (V + 15) / 16;
-    hipLaunchKernelGGL(unpack_bits_sel_kernel, dim3((unsigned)((nvec + 255) / 256), (unsigned)(B * P)), dim3(256), 0, st, packed, out, P, C, V, flags, force);
-    return rs_check_launch();
-}
-
-// flags[b * C + c] = any voxel of class c of sample b set, straight from the packed bytes: the OR over byte plane (b, p) holds the eight class flags of that plane
-// (bit 7 - k = class 8 p + k).  1/8 of the bytes rsuper_plane_any reads on the inflated volume.  flags must be zeroed first (plane_flags_zero_kernel).
-__global__ __launch_bounds__(256) void plane_any_bits_kernel(const uint8_t* __restrict__ packed, int P, int C, long V, uint8_t* __restrict__ flags) {
-    const int pl = blockIdx.y % P, b = blockIdx.y / P;
-    const uint8_t* src = packed + (size_t)blockIdx.y * V;
-    const long nvec = V / 16;
-    unsigned int any = 0;
-    const long stride = (long)gridDim.x * 256;
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    for (; i + 3 * stride < nvec; i += 4 * stride) {
-        const uint4 a = ((const uint4*)src)[i], b4 = ((const uint4*)src)[i + stride], c = ((const uint4*)src)[i + 2 * stride], d = ((const uint4*)src)[i + 3 * stride];
-        any |= (a.x | a.y | a.z | a.w) | (b4.x | b4.y | b4.z | b4.w) | (c.x | c.y | c.z | c.w) | (d.x | d.y | d.z | d.w);
-    }
-    for (; i < nvec; i += stride) {
-        const uint4 q = ((const uint4*)src)[i];
-        any |= q.x | q.y | q.z | q.w;
-    }
-    if (blockIdx.x == 0) for (long j = nvec * 16 + threadIdx.x; j < V; j += 256) any |= src[j];
-    any |= any >> 16; any |= any >> 8; any &= 0xFFu;             // fold the four byte lanes of the word
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) any |= __shfl_xor(any, o, 64);
-    if (any && (threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (((any >> (7 - k)) & 1u) && pl * 8 + k < C) flags[(size_t)b * C + pl * 8 + k] = 1;
-    }
-}
-int rs_launch_plane_any_bits(const uint8_t* packed, int B, int P, int C, long V, uint8_t* flags, hipStream_t st) {
-    hipLaunchKernelGGL(plane_flags_zero_kernel, dim3((unsigned)(((long)B * C + 255) / 256)), dim3(256), 0, st, flags, (long)B * C);
-    long nb = (V / 16 + 255) / 256;
-    if (nb > 32) nb = 32;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(plane_any_bits_kernel, dim3((unsigned)nb, (unsigned)(B * P)), dim3(256), 0, st, packed, P, C, V, flags);
-    return rs_check_launch();
-}
-
-// any(plane) for `planes` byte volumes of V voxels each: flags[p] = 1 if the plane has a non-zero byte.  Replaces the ATen
-// `.flatten(1).any(1)` reductions of the loss' host control flow (150 us each on a 46 MB uint8 tensor) at HBM rate.
-__global__ __launch_bounds__(256) void plane_any_kernel(const uint8_t* __restrict__ m, long V, uint8_t* __restrict__ flags) {
-    const uint8_t* pl = m + (size_t)blockIdx.y * V;
-    const long nvec = V / 16;
-    unsigned int any = 0;
-    const long stride = (long)gridDim.x * 256;
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    for (; i + 3 * stride < nvec; i += 4 * stride) {             // four independent 16-byte loads in flight per thread (one at a time ran at 1.4 TB/s)
-        const uint4 a = ((const uint4*)pl)[i], b = ((const uint4*)pl)[i + stride], c = ((const uint4*)pl)[i + 2 * stride], d = ((const uint4*)pl)[i + 3 * stride];
-        any |= (a.x | a.y | a.z | a.w) | (b.x | b.y | b.z | b.w) | (c.x | c.y | c.z | c.w) | (d.x | d.y | d.z | d.w);
-    }
-    for (; i < nvec; i += stride) {
-        const uint4 q = ((const uint4*)pl)[i];
-        any |= q.x | q.y | q.z | q.w;
-    }
-    if (blockIdx.x == 0) for (long j = nvec * 16 + threadIdx.x; j < V; j += 256) any |= pl[j];
-    if (__any(any != 0) && (threadIdx.x & 63) == 0) flags[blockIdx.y] = 1;
-}
-
-__global__ void plane_flags_zero_kernel(uint8_t* flags, long planes) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < planes) flags[i] = 0;
-}
-
 // The input range guards of train_epoch (train_ddp.py:311-313: isnan / max <= hi / min >= lo, three host synchronisations in the reference) as ONE pass
 // that only sets device flags: flags[0] |= any NaN, flags[1] |= any x > hi, flags[2] |= any x < lo.  The host reads the flags one step later.
 __global__ __launch_bounds__(256) void guard_range_kernel(const float* __restrict__ x, size_t n, float lo, float hi, int* __restrict__ flags) {
@@ -994,15 +789,6 @@ int rs_launch_guard_range(const float* x, size_t n, float lo, float hi, int* fla
     if (nb > 1024) nb = 1024;
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(guard_range_kernel, dim3((unsigned)nb), dim3(256), 0, st, x, n, lo, hi, flags);
-    return rs_check_launch();
-}
-
-int rs_launch_plane_any(const uint8_t* m, long planes, long V, uint8_t* flags, hipStream_t st) {
-    hipLaunchKernelGGL(plane_flags_zero_kernel, dim3((unsigned)((planes + 255) / 256)), dim3(256), 0, st, flags, planes);   // a kernel, not a memset node (optim.hip)
-    long nb = (V / 16 + 255) / 256;
-    if (nb > 32) nb = 32;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(plane_any_kernel, dim3((unsigned)nb, (unsigned)planes), dim3(256), 0, st, m, V, flags);
     return rs_check_launch();
 }
 

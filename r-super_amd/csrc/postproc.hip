@@ -5,11 +5,13 @@
 //   largest cc     keep_largest_component :692-716: 6-connected union-find, root = smallest linear index, largest size / first root
 // Every cross-workgroup result is an integer atomic (histogram bins, u64 max keys, union-find links): deterministic by construction.
 #include "common.hpp"
+#include "ccl.hpp"
 #include "../../include/rsuper_hip.h"
 
 namespace {
 
-constexpr int NT = 256;                                  // threads per block of every kernel below (4 waves)
+constexpr int NT = CCL_NT;                               // threads per block of every kernel below (4 waves)
+constexpr int GRID_CAP = 8192;                           // blocks of a grid-stride pass (tuned)
 
 // ------------------------------------------------------------------------------------------------ shared helpers
 // One separable box pass over a byte tile in LDS: d[z][y][x] = op(s[(z, y, x) + k * axis], k < K); d has the source extents minus K - 1 along AX.
@@ -27,24 +29,6 @@ __device__ __forceinline__ void box_pass(const uint8_t* s, uint8_t* d, int sz, i
         d[i] = v;
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-// order-preserving u64 image of an f64 (larger key <=> larger value; 0 is below every value)
-__device__ __forceinline__ unsigned long long f64_key(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_f64(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
 }
 
 // ------------------------------------------------------------------------------------------------ detection
@@ -235,118 +219,24 @@ __global__ __launch_bounds__(NT) void organ_mask_kernel(const T* __restrict__ pr
 }
 
 // ------------------------------------------------------------------------------------------------ largest connected component
-constexpr int CC_Z = 8, CC_Y = 8, CC_X = 32;             // block-local labelling tile
-constexpr uint32_t CC_BG = 0xFFFFFFFFu;                  // parent word of a background voxel
-
-__device__ __forceinline__ int lds_find(int* p, int a) {
-    int q;
-    while ((q = __hip_atomic_load(&p[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != a) a = q;
-    return a;
-}
-
-// union by atomicMin linking: the larger root is linked below the smaller one, so every parent <= its child and the root of a set is its
-// smallest index whatever the order the links land in
-__device__ __forceinline__ void lds_union(int* p, int a, int b) {
-    bool done = false;
-    while (!done) {
-        a = lds_find(p, a);
-        b = lds_find(p, b);
-        if (a < b) { const int old = atomicMin(&p[b], a); done = old == b; b = old; }
-        else if (b < a) { const int old = atomicMin(&p[a], b); done = old == a; a = old; }
-        else done = true;
-    }
-}
-
-// Parent words another workgroup may write: agent-scope atomic loads (a plain load can return a stale copy from another XCD's L2).
-__device__ __forceinline__ uint32_t g_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t g_find(const uint32_t* p, uint32_t a) {
-    uint32_t q;
-    while ((q = g_load(&p[a])) != a) a = q;
-    return a;
-}
-
-__device__ __forceinline__ void g_union(uint32_t* p, uint32_t a, uint32_t b) {
-    bool done = false;
-    while (!done) {
-        a = g_find(p, a);
-        b = g_find(p, b);
-        if (a < b) { const uint32_t old = atomicMin(&p[b], a); done = old == b; b = old; }
-        else if (b < a) { const uint32_t old = atomicMin(&p[a], b); done = old == a; a = old; }
-        else done = true;
-    }
-}
-
+// The labeller itself (tile pass, border pass, compression, the union-find and why its loads are agent-scope atomics) is ccl.hpp, 6-connected here.
 __device__ __forceinline__ bool fg(const uint8_t* m, long i) { return m[i] > 0; }
 __device__ __forceinline__ bool fg(const float* m, long i) { return m[i] > 0.f; }
 
-// (a) label one tile in LDS, write parent = global index of the tile-local root (background: CC_BG), zero the size counters and the key
+// (a) label one tile, zero the size counters and the key
 template <typename T>
 __global__ __launch_bounds__(NT) void cc_local_kernel(const T* __restrict__ m, uint32_t* __restrict__ parent, uint32_t* __restrict__ count,
                                                       unsigned long long* key, int D, int H, int W, int tiles_x, int tiles_y) {
-    constexpr int N = CC_Z * CC_Y * CC_X;
-    __shared__ int lp[N];
-    const int tile = blockIdx.x, tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / tiles_x / tiles_y;
-    const int oz = tz * CC_Z, oy = ty * CC_Y, ox = tx * CC_X;
-    for (int i = threadIdx.x; i < N; i += NT) {
-        const int lx = i % CC_X, t = i / CC_X, ly = t % CC_Y, lz = t / CC_Y;
-        const int gz = oz + lz, gy = oy + ly, gx = ox + lx;
-        bool f = false;
-        if (gz < D && gy < H && gx < W) {
-            const long gi = ((long)gz * H + gy) * W + gx;
-            f = fg(m, gi);
-            count[gi] = 0u;
-        }
-        lp[i] = f ? i : -1;
-    }
     if (blockIdx.x == 0 && threadIdx.x == 0) *key = 0ull;
-    __syncthreads();
-    for (int i = threadIdx.x; i < N; i += NT) {
-        if (lp[i] < 0) continue;                         // foreground words stay >= 0 under the unions, background stays -1
-        const int lx = i % CC_X, ly = (i / CC_X) % CC_Y, lz = i / (CC_X * CC_Y);
-        if (lx > 0 && lp[i - 1] >= 0) lds_union(lp, i, i - 1);
-        if (ly > 0 && lp[i - CC_X] >= 0) lds_union(lp, i, i - CC_X);
-        if (lz > 0 && lp[i - CC_X * CC_Y] >= 0) lds_union(lp, i, i - CC_X * CC_Y);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < N; i += NT) {
-        const int lx = i % CC_X, t = i / CC_X, ly = t % CC_Y, lz = t / CC_Y;
-        const int gz = oz + lz, gy = oy + ly, gx = ox + lx;
-        if (gz >= D || gy >= H || gx >= W) continue;
-        uint32_t v = CC_BG;
-        if (lp[i] >= 0) {
-            const int r = lds_find(lp, i);
-            const int rx = r % CC_X, rt = r / CC_X, ry = rt % CC_Y, rz = rt / CC_Y;
-            v = (uint32_t)((((long)(oz + rz)) * H + oy + ry) * W + ox + rx);
-        }
-        parent[((long)gz * H + gy) * W + gx] = v;
-    }
+    ccl_label_tile<6>(parent, blockIdx.x, tiles_x, tiles_y, D, H, W, [&](long gi) {
+        count[gi] = 0u;
+        return fg(m, gi);
+    });
 }
 
 // (b) link across the three low faces of every tile
 __global__ __launch_bounds__(NT) void cc_merge_kernel(uint32_t* parent, int D, int H, int W, int tiles_x, int tiles_y) {
-    const int tile = blockIdx.x, tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / tiles_x / tiles_y;
-    const int oz = tz * CC_Z, oy = ty * CC_Y, ox = tx * CC_X;
-    constexpr int FX = CC_Z * CC_Y, FY = CC_Z * CC_X, FZ = CC_Y * CC_X;
-    for (int j = threadIdx.x; j < FX + FY + FZ; j += NT) {
-        int lz, ly, lx;
-        long step;
-        if (j < FX) {
-            if (ox == 0) continue;
-            lz = j / CC_Y; ly = j % CC_Y; lx = 0; step = 1;
-        } else if (j < FX + FY) {
-            if (oy == 0) continue;
-            lz = (j - FX) / CC_X; lx = (j - FX) % CC_X; ly = 0; step = W;
-        } else {
-            if (oz == 0) continue;
-            ly = (j - FX - FY) / CC_X; lx = (j - FX - FY) % CC_X; lz = 0; step = (long)H * W;
-        }
-        const int gz = oz + lz, gy = oy + ly, gx = ox + lx;
-        if (gz >= D || gy >= H || gx >= W) continue;
-        const long a = ((long)gz * H + gy) * W + gx;
-        if (g_load(&parent[a]) == CC_BG || g_load(&parent[a - step]) == CC_BG) continue;
-        g_union(parent, (uint32_t)a, (uint32_t)(a - step));
-    }
+    ccl_link_borders<6>(parent, blockIdx.x, tiles_x, tiles_y, D, H, W);
 }
 
 // (c) path compression + component sizes: one counter add per distinct root in a wave
@@ -357,12 +247,8 @@ __global__ __launch_bounds__(NT) void cc_compress_kernel(uint32_t* parent, uint3
         bool act = false;
         uint32_t r = 0;
         if (i < n) {
-            const uint32_t q = g_load(&parent[i]);
-            if (q != CC_BG) {
-                r = g_find(parent, q);
-                if (r != q) __hip_atomic_store(&parent[i], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                act = true;
-            }
+            r = ccl_compress(parent, i);
+            act = r != CCL_BG;
         }
         unsigned long long pend = __ballot(act);
         while (pend) {
@@ -399,13 +285,6 @@ __global__ __launch_bounds__(NT) void cc_write_kernel(const uint32_t* __restrict
         out[i] = k == 0ull ? 1 : (parent[i] == sel ? 1 : 0);
 }
 
-int grid_for(long n) {
-    const long b = (n + NT - 1) / NT;
-    return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192);
-}
-
-bool launched() { return hipGetLastError() == hipSuccess; }
-
 template <typename T>
 int organ_mask_launch(const T* pred, int D, int H, int W, int n, const int* lesion, const int* organ_a, const int* organ_b, T* out, hipStream_t st) {
     const int tx = (W + OM_X - 1) / OM_X, ty = (H + OM_Y - 1) / OM_Y, tz = (D + OM_Z - 1) / OM_Z;
@@ -414,7 +293,7 @@ int organ_mask_launch(const T* pred, int D, int H, int W, int n, const int* lesi
         OrganPlanes pl;
         for (int k = 0; k < nk; ++k) { pl.les[k] = lesion[k0 + k]; pl.oa[k] = organ_a[k0 + k]; pl.ob[k] = organ_b[k0 + k]; }
         hipLaunchKernelGGL(organ_mask_kernel<T>, dim3(tx * ty * tz, nk), dim3(NT), 0, st, pred, out + (long)k0 * D * H * W, pl, D, H, W, tx, ty);
-        if (!launched()) return RS_ERR_LAUNCH;
+        if (rs_check_launch() != RS_OK) return RS_ERR_LAUNCH;
     }
     return RS_OK;
 }
@@ -425,13 +304,13 @@ int largest_component_launch(const T* m, int D, int H, int W, uint8_t* out, void
     unsigned long long* key = (unsigned long long*)ws;
     uint32_t* parent = (uint32_t*)((char*)ws + 256);
     uint32_t* count = parent + ((n + 63) & ~63L);
-    const int tx = (W + CC_X - 1) / CC_X, ty = (H + CC_Y - 1) / CC_Y, tz = (D + CC_Z - 1) / CC_Z;
+    const int tx = (W + CCL_X - 1) / CCL_X, ty = (H + CCL_Y - 1) / CCL_Y, tz = (D + CCL_Z - 1) / CCL_Z;
     hipLaunchKernelGGL(cc_local_kernel<T>, dim3(tx * ty * tz), dim3(NT), 0, st, m, parent, count, key, D, H, W, tx, ty);
     hipLaunchKernelGGL(cc_merge_kernel, dim3(tx * ty * tz), dim3(NT), 0, st, parent, D, H, W, tx, ty);
-    hipLaunchKernelGGL(cc_compress_kernel, dim3(grid_for(n)), dim3(NT), 0, st, parent, count, n);
-    hipLaunchKernelGGL(cc_pick_kernel, dim3(grid_for(n)), dim3(NT), 0, st, (const uint32_t*)count, n, key);
-    hipLaunchKernelGGL(cc_write_kernel, dim3(grid_for(n)), dim3(NT), 0, st, (const uint32_t*)parent, (const unsigned long long*)key, n, out);
-    return launched() ? RS_OK : RS_ERR_LAUNCH;
+    hipLaunchKernelGGL(cc_compress_kernel, dim3(grid_for(n, GRID_CAP)), dim3(NT), 0, st, parent, count, n);
+    hipLaunchKernelGGL(cc_pick_kernel, dim3(grid_for(n, GRID_CAP)), dim3(NT), 0, st, (const uint32_t*)count, n, key);
+    hipLaunchKernelGGL(cc_write_kernel, dim3(grid_for(n, GRID_CAP)), dim3(NT), 0, st, (const uint32_t*)parent, (const unsigned long long*)key, n, out);
+    return rs_check_launch();
 }
 
 bool dims_ok(int D, int H, int W) { return D > 0 && H > 0 && W > 0 && (long)D * H * W <= (1L << 31); }
@@ -461,14 +340,14 @@ int rsuper_detection(const float* x, int planes, int Di, int Hi, int Wi, int Do,
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* ws = (unsigned long long*)workspace;
     const long nws = (long)planes * (DT_BINS + 1);
-    hipLaunchKernelGGL(detect_zero_kernel, dim3(grid_for(nws)), dim3(NT), 0, st, ws, nws);
+    hipLaunchKernelGGL(detect_zero_kernel, dim3(grid_for(nws, GRID_CAP)), dim3(NT), 0, st, ws, nws);
     const int tx = (Wo + DT_X - 1) / DT_X, ty = (Ho + DT_Y - 1) / DT_Y, tz = (Do + DT_Z - 1) / DT_Z;
     const dim3 grid(tx * ty * tz, planes);
     const long in_plane = (long)Di * Hi * Wi;
     if (erode) hipLaunchKernelGGL(detect_kernel<true>, grid, dim3(NT), 0, st, x, in_plane, g, th, nthr, tx, ty, ws);
     else hipLaunchKernelGGL(detect_kernel<false>, grid, dim3(NT), 0, st, x, in_plane, g, th, nthr, tx, ty, ws);
     hipLaunchKernelGGL(detect_finalize_kernel, dim3(planes), dim3(NT), 0, st, (const unsigned long long*)ws, nthr, volumes, max_prob);
-    return launched() ? RS_OK : RS_ERR_LAUNCH;
+    return rs_check_launch();
 }
 
 int rsuper_organ_mask_u8(const uint8_t* pred, int C, int D, int H, int W, int n, const int* lesion, const int* organ_a, const int* organ_b,

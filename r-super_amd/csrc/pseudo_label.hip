@@ -16,14 +16,13 @@
 //   root        pl_count block 0
 //   kept, iterations   pl_apply block 0
 #include "common.hpp"
+#include "ccl.hpp"
 #include "../../include/rsuper_hip.h"
 
 namespace {
 
-constexpr int NT = 256;                                  // threads per block (4 waves)
-constexpr int PL_Z = 8, PL_Y = 8, PL_X = 32;             // block-local labelling tile
-constexpr int PL_N = PL_Z * PL_Y * PL_X;
-constexpr uint32_t PL_BG = 0xFFFFFFFFu;                  // parent word of a voxel outside the mask
+constexpr int NT = CCL_NT;                               // threads per block (4 waves)
+constexpr int GRID_CAP = 2048;                           // blocks of a grid-stride pass (tuned)
 constexpr int PL_MAX_PLANES = RSUPER_LESION_MAX_PLANES;
 
 struct PlaneState {                                      // RSUPER_LESION_STATE_WORDS 32-bit words per plane
@@ -34,67 +33,6 @@ struct PlaneState {                                      // RSUPER_LESION_STATE_
 static_assert(sizeof(PlaneState) == RSUPER_LESION_STATE_WORDS * 4, "state layout");
 
 struct Counts { int n[PL_MAX_PLANES]; };
-
-// order-preserving u32 image of an f32 (larger key <=> larger value)
-__device__ __forceinline__ uint32_t f32_key(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7FFFFFFFu) : ~k); }
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int lds_find(int* p, int a) {
-    int q;
-    while ((q = __hip_atomic_load(&p[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != a) a = q;
-    return a;
-}
-
-// union by atomicMin linking: every parent <= its child, the root of a set is its smallest index whatever the order the links land in
-__device__ __forceinline__ void lds_union(int* p, int a, int b) {
-    bool done = false;
-    while (!done) {
-        a = lds_find(p, a);
-        b = lds_find(p, b);
-        if (a < b) { const int old = atomicMin(&p[b], a); done = old == b; b = old; }
-        else if (b < a) { const int old = atomicMin(&p[a], b); done = old == a; a = old; }
-        else done = true;
-    }
-}
-
-// Parent words another workgroup may write: agent-scope atomic loads (a plain load can return a stale copy from another XCD's L2).
-__device__ __forceinline__ uint32_t g_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t g_find(const uint32_t* p, uint32_t a) {
-    uint32_t q;
-    while ((q = g_load(&p[a])) != a) a = q;
-    return a;
-}
-
-__device__ __forceinline__ void g_union(uint32_t* p, uint32_t a, uint32_t b) {
-    bool done = false;
-    while (!done) {
-        a = g_find(p, a);
-        b = g_find(p, b);
-        if (a < b) { const uint32_t old = atomicMin(&p[b], a); done = old == b; b = old; }
-        else if (b < a) { const uint32_t old = atomicMin(&p[a], b); done = old == a; a = old; }
-        else done = true;
-    }
-}
-
-// the k-th of the 13 neighbours that precede a voxel in C order: k 0..8 -> dz = -1, (dy, dx) in [-1, 1]^2; 9..11 -> dz = 0, dy = -1; 12 -> dx = -1
-__device__ __forceinline__ void backward(int k, int& dz, int& dy, int& dx) {
-    if (k < 9) { dz = -1; dy = k / 3 - 1; dx = k % 3 - 1; }
-    else if (k < 12) { dz = 0; dy = -1; dx = k - 10; }
-    else { dz = 0; dy = 0; dx = -1; }
-}
 
 // out = 0 and the state of every plane: one launch, no memset (a captured hipMemsetAsync is what README round 3 warns about)
 __global__ __launch_bounds__(NT) void pl_begin_kernel(uint8_t* __restrict__ out, long total, PlaneState* st, Counts c, int planes) {
@@ -121,10 +59,9 @@ __global__ __launch_bounds__(NT) void pl_peak_kernel(const float* __restrict__ w
     if ((threadIdx.x & 63) == 0 && best) atomicMax(&s->key, best);
 }
 
-// (2) stop or go; label one tile of work >= thr in LDS, parent = global index of the tile-local root (outside the mask: PL_BG)
+// (2) stop or go; label one tile of work >= thr in LDS, parent = global index of the tile-local root (outside the mask: CCL_BG)
 __global__ __launch_bounds__(NT) void pl_local_kernel(const float* __restrict__ work, uint32_t* __restrict__ parent, long n, long pstride, PlaneState* st,
                                                       float peak_cut, float min_peak, int D, int H, int W, int tiles_x, int tiles_y) {
-    __shared__ int lp[PL_N];
     PlaneState* s = st + blockIdx.y;
     if (s->done) return;
     const unsigned long long key = s->key;
@@ -138,76 +75,13 @@ __global__ __launch_bounds__(NT) void pl_local_kernel(const float* __restrict__ 
     if (stop) return;
     const float thr = __fmul_rn(peak_cut, peak);
     const float* w = work + (long)blockIdx.y * n;
-    uint32_t* par = parent + (long)blockIdx.y * pstride;
-    const int tile = blockIdx.x, tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / tiles_x / tiles_y;
-    const int oz = tz * PL_Z, oy = ty * PL_Y, ox = tx * PL_X;
-    for (int i = threadIdx.x; i < PL_N; i += NT) {
-        const int lx = i % PL_X, t = i / PL_X, ly = t % PL_Y, lz = t / PL_Y;
-        const int gz = oz + lz, gy = oy + ly, gx = ox + lx;
-        bool f = false;
-        if (gz < D && gy < H && gx < W) f = w[((long)gz * H + gy) * W + gx] >= thr;
-        lp[i] = f ? i : -1;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < PL_N; i += NT) {
-        if (lp[i] < 0) continue;                         // mask words stay >= 0 under the unions, the others stay -1
-        const int lx = i % PL_X, t = i / PL_X, ly = t % PL_Y, lz = t / PL_Y;
-        for (int k = 0; k < 13; ++k) {
-            int dz, dy, dx;
-            backward(k, dz, dy, dx);
-            const int nz = lz + dz, ny = ly + dy, nx = lx + dx;
-            if (nz < 0 || ny < 0 || ny >= PL_Y || nx < 0 || nx >= PL_X) continue;
-            const int j = (nz * PL_Y + ny) * PL_X + nx;
-            if (lp[j] >= 0) lds_union(lp, i, j);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < PL_N; i += NT) {
-        const int lx = i % PL_X, t = i / PL_X, ly = t % PL_Y, lz = t / PL_Y;
-        const int gz = oz + lz, gy = oy + ly, gx = ox + lx;
-        if (gz >= D || gy >= H || gx >= W) continue;
-        uint32_t v = PL_BG;
-        if (lp[i] >= 0) {
-            const int r = lds_find(lp, i);
-            const int rx = r % PL_X, rt = r / PL_X, ry = rt % PL_Y, rz = rt / PL_Y;
-            v = (uint32_t)((((long)(oz + rz)) * H + oy + ry) * W + ox + rx);
-        }
-        par[((long)gz * H + gy) * W + gx] = v;
-    }
+    ccl_label_tile<26>(parent + (long)blockIdx.y * pstride, blockIdx.x, tiles_x, tiles_y, D, H, W, [&](long gi) { return w[gi] >= thr; });
 }
 
-// (3) every voxel with a backward neighbour outside its tile links to it: the low z / y / x faces and, for (dz, dy, dx) such as (-1, +1, +1) or
-// (0, -1, +1), the high y and x faces too -- face-, edge- and corner-adjacent tiles alike
+// (3) every mask voxel with a backward neighbour outside its tile links to it (ccl.hpp: the low z / y / x faces and the high y and x faces)
 __global__ __launch_bounds__(NT) void pl_merge_kernel(uint32_t* parent, long pstride, const PlaneState* st, int D, int H, int W, int tiles_x, int tiles_y) {
     if (st[blockIdx.y].done) return;
-    uint32_t* par = parent + (long)blockIdx.y * pstride;
-    const int tile = blockIdx.x, tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / tiles_x / tiles_y;
-    const int oz = tz * PL_Z, oy = ty * PL_Y, ox = tx * PL_X;
-    for (int i = threadIdx.x; i < PL_N; i += NT) {
-        const int lx = i % PL_X, t = i / PL_X, ly = t % PL_Y, lz = t / PL_Y;
-        if (lz != 0 && ly != 0 && ly != PL_Y - 1 && lx != 0 && lx != PL_X - 1) continue;       // every backward neighbour lies inside the tile
-        const int gz = oz + lz, gy = oy + ly, gx = ox + lx;
-        if (gz >= D || gy >= H || gx >= W) continue;
-        const long a = ((long)gz * H + gy) * W + gx;
-        const uint32_t pa = g_load(&par[a]);
-        if (pa == PL_BG) continue;
-        uint32_t last = PL_BG;                           // the neighbour word this voxel linked to last
-        for (int k = 0; k < 13; ++k) {
-            int dz, dy, dx;
-            backward(k, dz, dy, dx);
-            const int nz = lz + dz, ny = ly + dy, nx = lx + dx;
-            if (nz >= 0 && ny >= 0 && ny < PL_Y && nx >= 0 && nx < PL_X) continue;              // inside the tile: linked by pl_local
-            const int hz = gz + dz, hy = gy + dy, hx = gx + dx;
-            if (hz < 0 || hy < 0 || hy >= H || hx < 0 || hx >= W) continue;                      // outside the volume (hz < D: dz <= 0)
-            const long b = ((long)hz * H + hy) * W + hx;
-            // parent words never leave their set, so two neighbours with the same word are in one set already: on a smooth mask the up to nine
-            // outside neighbours of a face voxel mostly share one tile root, and one request does for all of them
-            const uint32_t pb = g_load(&par[b]);
-            if (pb == PL_BG || pb == last) continue;
-            g_union(par, pa, pb);
-            last = pb;
-        }
-    }
+    ccl_link_borders<26>(parent + (long)blockIdx.y * pstride, blockIdx.x, tiles_x, tiles_y, D, H, W);
 }
 
 // (4) path compression and the size of the seed's component: one counter add per wave
@@ -219,19 +93,16 @@ __global__ __launch_bounds__(NT) void pl_count_kernel(uint32_t* parent, long n, 
     if (threadIdx.x == 0) {
         const uint32_t seed = (uint32_t)(0xFFFFFFFFull - (s->key & 0xFFFFFFFFull));
         // root words do not change in this launch: every block finds the same one.  A finite peak lies inside its own mask (thr <= peak for
-        // 0 < peak_cut <= 1); were the seed ever outside it, its word is PL_BG, which is no index: nothing is followed and pl_apply ends the plane
-        seed_root = g_load(&par[seed]) == PL_BG ? PL_BG : g_find(par, seed);
+        // 0 < peak_cut <= 1); were the seed ever outside it, its word is CCL_BG, which is no index: nothing is followed and pl_apply ends the plane
+        seed_root = g_load(&par[seed]) == CCL_BG ? CCL_BG : g_find(par, seed);
         if (blockIdx.x == 0) s->root = seed_root;
     }
     __syncthreads();
     const uint32_t root = seed_root;
     uint32_t mine = 0u;
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
-        const uint32_t q = g_load(&par[i]);
-        if (q == PL_BG) continue;
-        const uint32_t r = g_find(par, q);
-        if (r != q) __hip_atomic_store(&par[i], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        mine += r == root ? 1u : 0u;
+        const uint32_t r = ccl_compress(par, i);
+        mine += r != CCL_BG && r == root ? 1u : 0u;      // root itself is CCL_BG when the seed has no component
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
@@ -244,7 +115,7 @@ __global__ __launch_bounds__(NT) void pl_apply_kernel(float* __restrict__ work, 
     PlaneState* s = st + blockIdx.y;
     if (s->done) return;
     const uint32_t root = s->root;
-    if (root == PL_BG) {                                 // no seed component (see pl_count): nothing to zero, so the plane could not advance -- end it
+    if (root == CCL_BG) {                                 // no seed component (see pl_count): nothing to zero, so the plane could not advance -- end it
         if (blockIdx.x == 0 && threadIdx.x == 0) s->done = 1;
         return;
     }
@@ -263,13 +134,6 @@ __global__ __launch_bounds__(NT) void pl_apply_kernel(float* __restrict__ work, 
         s->key = 0ull;
     }
 }
-
-int grid_for(long n) {
-    const long b = (n + NT - 1) / NT;
-    return (int)(b < 2048 ? (b > 0 ? b : 1) : 2048);
-}
-
-bool launched() { return hipGetLastError() == hipSuccess; }
 
 bool shape_ok(int planes, int D, int H, int W) {
     return planes >= 1 && planes <= PL_MAX_PLANES && D > 0 && H > 0 && W > 0 && (long)D * H * W <= (1L << 31);
@@ -291,8 +155,8 @@ int rsuper_lesion_candidates_begin(uint8_t* out, int planes, int D, int H, int W
     Counts c;
     for (int p = 0; p < PL_MAX_PLANES; ++p) c.n[p] = p < planes ? n_lesions[p] : 0;
     const long total = (long)planes * D * H * W;
-    hipLaunchKernelGGL(pl_begin_kernel, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, out, total, (PlaneState*)state, c, planes);
-    return launched() ? RS_OK : RS_ERR_LAUNCH;
+    hipLaunchKernelGGL(pl_begin_kernel, dim3(grid_for(total, GRID_CAP)), dim3(NT), 0, (hipStream_t)stream, out, total, (PlaneState*)state, c, planes);
+    return rs_check_launch();
 }
 
 int rsuper_lesion_candidates_run(float* work, uint8_t* out, int planes, int D, int H, int W, float peak_cut, int min_voxels, float min_peak, void* state,
@@ -303,15 +167,15 @@ int rsuper_lesion_candidates_run(float* work, uint8_t* out, int planes, int D, i
     PlaneState* s = (PlaneState*)state;
     uint32_t* parent = (uint32_t*)workspace;
     const long n = (long)D * H * W, ps = parent_stride(n);
-    const int tx = (W + PL_X - 1) / PL_X, ty = (H + PL_Y - 1) / PL_Y, tz = (D + PL_Z - 1) / PL_Z;
-    const dim3 tiles(tx * ty * tz, planes), flat(grid_for(n), planes);
+    const int tx = (W + CCL_X - 1) / CCL_X, ty = (H + CCL_Y - 1) / CCL_Y, tz = (D + CCL_Z - 1) / CCL_Z;
+    const dim3 tiles(tx * ty * tz, planes), flat(grid_for(n, GRID_CAP), planes);
     for (int it = 0; it < iterations; ++it) {
         hipLaunchKernelGGL(pl_peak_kernel, flat, dim3(NT), 0, st, (const float*)work, n, s);
         hipLaunchKernelGGL(pl_local_kernel, tiles, dim3(NT), 0, st, (const float*)work, parent, n, ps, s, peak_cut, min_peak, D, H, W, tx, ty);
         hipLaunchKernelGGL(pl_merge_kernel, tiles, dim3(NT), 0, st, parent, ps, (const PlaneState*)s, D, H, W, tx, ty);
         hipLaunchKernelGGL(pl_count_kernel, flat, dim3(NT), 0, st, parent, n, ps, s);
         hipLaunchKernelGGL(pl_apply_kernel, flat, dim3(NT), 0, st, work, out, (const uint32_t*)parent, n, ps, s, min_voxels);
-        if (!launched()) return RS_ERR_LAUNCH;
+        if (rs_check_launch() != RS_OK) return RS_ERR_LAUNCH;
     }
     return RS_OK;
 }

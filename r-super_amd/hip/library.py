@@ -174,145 +174,83 @@ def install_loss_ops(lf):
     lf._LIBRARY_INSTALLED = True
 
 
-_PP_OPS = None
+_PLAIN_GROUPS = {}
+
+
+def _install_plain(group, ops):
+    """Register the (op name, schema, function) entries of `group` as plain CUDA kernels on first use; the registered ops, in order."""
+    if group not in _PLAIN_GROUPS:
+        _PLAIN_GROUPS[group] = tuple(_register_plain(name, schema, fn) for name, schema, fn in ops)
+    return _PLAIN_GROUPS[group]
 
 
 def install_postprocess_ops(detection_volumes, organ_mask, largest_component):
-    """Register the prediction post-processing operators of inference/detection.py and inference/postprocess.py (called at the end of
-    postprocess.py; idempotent) as plain CUDA kernels: integer volumes, masks and labels have no derivative."""
-    global _PP_OPS
-    if _PP_OPS is None:
-        _PP_OPS = (
-            _register_plain('detection_volumes', '(Tensor x, int[] out_shape, float[] thresholds, bool erode, Tensor? workspace=None) -> (Tensor, Tensor)',
-                            detection_volumes),
-            _register_plain('organ_mask', '(Tensor pred, int[] lesion, int[] organ_a, int[] organ_b) -> Tensor', organ_mask),
-            _register_plain('largest_component', '(Tensor mask, Tensor? workspace=None) -> Tensor', largest_component),
-        )
-    return _PP_OPS
-
-
-_AUG_OP = None
+    """The prediction post-processing operators of inference/detection.py and inference/postprocess.py (called at the end of postprocess.py): integer
+    volumes, masks and labels have no derivative."""
+    return _install_plain('postprocess', (
+        ('detection_volumes', '(Tensor x, int[] out_shape, float[] thresholds, bool erode, Tensor? workspace=None) -> (Tensor, Tensor)', detection_volumes),
+        ('organ_mask', '(Tensor pred, int[] lesion, int[] organ_a, int[] organ_b) -> Tensor', organ_mask),
+        ('largest_component', '(Tensor mask, Tensor? workspace=None) -> Tensor', largest_component)))
 
 
 def install_augment_ops(affine_crop):
-    """Register the spatial augmentation operator of training/augmentation.py (on its first use; idempotent) as a plain CUDA kernel: a resampled crop
-    of the loader's input has no derivative."""
-    global _AUG_OP
-    if _AUG_OP is None:
-        _AUG_OP = _register_plain('affine_crop', '(Tensor img, Tensor[] volumes, Tensor theta, int[] out_size, int[] offsets) -> (Tensor, Tensor[])',
-                                  affine_crop)
-    return _AUG_OP
-
-
-_CROP_OPS = None
+    """The spatial augmentation operator of training/augmentation.py (on its first use): a resampled crop of the loader's input has no derivative."""
+    return _install_plain('augment', (
+        ('affine_crop', '(Tensor img, Tensor[] volumes, Tensor theta, int[] out_size, int[] offsets) -> (Tensor, Tensor[])', affine_crop),))[0]
 
 
 def install_crop_ops(class_counts, select_voxel, crop_box):
-    """Register the crop-on-tumour operators of training/augmentation.py (on their first use; idempotent) as plain CUDA kernels: counts, a voxel
-    index and a copied box have no derivative."""
-    global _CROP_OPS
-    if _CROP_OPS is None:
-        _CROP_OPS = (
-            _register_plain('class_counts', '(Tensor packed, int C, bool plain, Tensor? workspace=None) -> (Tensor, Tensor)', class_counts),
-            _register_plain('select_voxel', '(Tensor packed, int C, bool plain, Tensor table, int b, int column, int k, int count, int[] add) -> Tensor',
-                            select_voxel),
-            _register_plain('crop_box', '(Tensor? img, Tensor[] volumes, int[] size, int[] pad, Tensor? center, int[] origin) -> (Tensor, Tensor[], Tensor)',
-                            crop_box),
-        )
-    return _CROP_OPS
-
-
-_REPORT_CROP_OPS = None
+    """The crop-on-tumour operators of training/augmentation.py (on their first use): counts, a voxel index and a copied box have no derivative."""
+    return _install_plain('crop', (
+        ('class_counts', '(Tensor packed, int C, bool plain, Tensor? workspace=None) -> (Tensor, Tensor)', class_counts),
+        ('select_voxel', '(Tensor packed, int C, bool plain, Tensor table, int b, int column, int k, int count, int[] add) -> Tensor', select_voxel),
+        ('crop_box', '(Tensor? img, Tensor[] volumes, int[] size, int[] pad, Tensor? center, int[] origin) -> (Tensor, Tensor[], Tensor)', crop_box)))
 
 
 def install_report_crop_ops(union_bbox, union_bits, bits_open, label_remap):
-    """Register the report-crop operators of training/augmentation.py (on their first use; idempotent) as plain CUDA kernels: counts, boxes, bit
-    masks and remapped labels have no derivative.  Class sets are 64-bit sets as signed ints (the schema has no unsigned type)."""
-    global _REPORT_CROP_OPS
-    if _REPORT_CROP_OPS is None:
-        _REPORT_CROP_OPS = (
-            _register_plain('union_bbox', '(Tensor packed, int C, bool plain, int[] sets) -> Tensor', union_bbox),
-            _register_plain('union_bits', '(Tensor packed, int C, bool plain, int b, int set, int[] box) -> Tensor', union_bits),
-            _register_plain('bits_open', '(Tensor bits, int nx, int r, int[] add) -> (Tensor, Tensor, Tensor)', bits_open),
-            _register_plain('label_remap', '(Tensor packed, int C_in, int C_out, int nvol, int[] masks, int[] ones) -> Tensor[]', label_remap),
-        )
-    return _REPORT_CROP_OPS
-
-
-_PACK_OP = None
+    """The report-crop operators of training/augmentation.py (on their first use): counts, boxes, bit masks and remapped labels have no derivative.
+    Class sets are 64-bit sets as signed ints (the schema has no unsigned type)."""
+    return _install_plain('report_crop', (
+        ('union_bbox', '(Tensor packed, int C, bool plain, int[] sets) -> Tensor', union_bbox),
+        ('union_bits', '(Tensor packed, int C, bool plain, int b, int set, int[] box) -> Tensor', union_bits),
+        ('bits_open', '(Tensor bits, int nx, int r, int[] add) -> (Tensor, Tensor, Tensor)', bits_open),
+        ('label_remap', '(Tensor packed, int C_in, int C_out, int nvol, int[] masks, int[] ones) -> Tensor[]', label_remap)))
 
 
 def install_pack_ops(pack_bits):
-    """Register the label packing operator of training/dataset/packed.py (on its first use; idempotent) as a plain CUDA kernel: packed label bits have
-    no derivative."""
-    global _PACK_OP
-    if _PACK_OP is None:
-        _PACK_OP = _register_plain('pack_bits', '(Tensor volume) -> Tensor', pack_bits)
-    return _PACK_OP
-
-
-_INTENSITY_OP = None
+    """The label packing operator of training/dataset/packed.py (on its first use): packed label bits have no derivative."""
+    return _install_plain('pack', (('pack_bits', '(Tensor volume) -> Tensor', pack_bits),))[0]
 
 
 def install_intensity_ops(intensity_augment):
-    """Register the intensity augmentation operator of training/augmentation.py (on its first use; idempotent) as a plain CUDA kernel: the loader's
-    input has no derivative.  seeds are the 64-bit Philox keys as signed ints (the schema has no unsigned type)."""
-    global _INTENSITY_OP
-    if _INTENSITY_OP is None:
-        _INTENSITY_OP = _register_plain('intensity_augment', '(Tensor img, int[] flags, float[] scalars, int[] radius, float[] taps, int[] seeds, '
-                                        'Tensor? noise=None, Tensor? workspace=None) -> Tensor', intensity_augment)
-    return _INTENSITY_OP
-
-
-_PREPROCESS_OP = None
+    """The intensity augmentation operator of training/augmentation.py (on its first use): the loader's input has no derivative.  seeds are the 64-bit
+    Philox keys as signed ints (the schema has no unsigned type)."""
+    return _install_plain('intensity', (
+        ('intensity_augment', '(Tensor img, int[] flags, float[] scalars, int[] radius, float[] taps, int[] seeds, '
+         'Tensor? noise=None, Tensor? workspace=None) -> Tensor', intensity_augment),))[0]
 
 
 def install_preprocess_ops(ct_normalize):
-    """Register the whole-CT z-score of inference/preprocess.py (at the end of that module; idempotent) as a plain CUDA kernel: the network's input
-    has no derivative."""
-    global _PREPROCESS_OP
-    if _PREPROCESS_OP is None:
-        _PREPROCESS_OP = _register_plain('ct_normalize', '(Tensor hu, float lo, float hi, int[] out_shape, int[] offset, Tensor? workspace=None) '
-                                         '-> (Tensor, Tensor)', ct_normalize)
-    return _PREPROCESS_OP
-
-
-_RESAMPLE_OP = None
+    """The whole-CT z-score of inference/preprocess.py (at the end of that module): the network's input has no derivative."""
+    return _install_plain('preprocess', (
+        ('ct_normalize', '(Tensor hu, float lo, float hi, int[] out_shape, int[] offset, Tensor? workspace=None) -> (Tensor, Tensor)', ct_normalize),))[0]
 
 
 def install_resample_ops(resample3d):
-    """Register the class-stack resampler of inference/resample.py (at the end of that module; idempotent) as a plain CUDA kernel: labels and
-    thresholded probabilities have no derivative."""
-    global _RESAMPLE_OP
-    if _RESAMPLE_OP is None:
-        _RESAMPLE_OP = _register_plain('resample3d', '(Tensor x, int[] box, int[] out_size, str interp, float? threshold=None) -> Tensor', resample3d)
-    return _RESAMPLE_OP
-
-
-_METRIC_OPS = None
+    """The class-stack resampler of inference/resample.py (at the end of that module): labels and thresholded probabilities have no derivative."""
+    return _install_plain('resample', (
+        ('resample3d', '(Tensor x, int[] box, int[] out_size, str interp, float? threshold=None) -> Tensor', resample3d),))[0]
 
 
 def install_metric_ops(surface_distances, edt3):
-    """Register the validation-metric operators of metric/metrics.py (at the end of that module's setup; idempotent) as plain CUDA kernels:
-    distances between mask surfaces have no derivative."""
-    global _METRIC_OPS
-    if _METRIC_OPS is None:
-        _METRIC_OPS = (
-            _register_plain('surface_distances', '(Tensor mask_gt, Tensor mask_pred, float[] spacing, Tensor area_table) -> (Tensor[], Tensor)',
-                            surface_distances),
-            _register_plain('edt3', '(Tensor codes, int[] box, float[] spacing, Tensor? workspace=None) -> Tensor', edt3),
-        )
-    return _METRIC_OPS
-
-
-_PSEUDO_LABEL_OP = None
+    """The validation-metric operators of metric/metrics.py (at the end of that module's setup): distances between mask surfaces have no derivative."""
+    return _install_plain('metric', (
+        ('surface_distances', '(Tensor mask_gt, Tensor mask_pred, float[] spacing, Tensor area_table) -> (Tensor[], Tensor)', surface_distances),
+        ('edt3', '(Tensor codes, int[] box, float[] spacing, Tensor? workspace=None) -> Tensor', edt3)))
 
 
 def install_pseudo_label_ops(lesion_candidates):
-    """Register the lesion-candidate extraction of baselines/pseudo_labels (at the end of that module; idempotent) as a plain CUDA kernel: masks and
-    counters have no derivative."""
-    global _PSEUDO_LABEL_OP
-    if _PSEUDO_LABEL_OP is None:
-        _PSEUDO_LABEL_OP = _register_plain('lesion_candidates', '(Tensor prob, int[] n_lesions, float peak_cut, int min_voxels, float min_peak, int batch) '
-                                           '-> (Tensor mask, Tensor state)', lesion_candidates)
-    return _PSEUDO_LABEL_OP
+    """The lesion-candidate extraction of baselines/pseudo_labels (at the end of that module): masks and counters have no derivative."""
+    return _install_plain('pseudo_label', (
+        ('lesion_candidates', '(Tensor prob, int[] n_lesions, float peak_cut, int min_voxels, float min_peak, int batch) -> (Tensor mask, Tensor state)',
+         lesion_candidates),))[0]

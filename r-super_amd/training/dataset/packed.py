@@ -69,7 +69,7 @@ def _pack_op():
 
 def pack_bits_device(volume):
     """volume: int8 / uint8 / bool device tensor (B, C, D, H, W) or (C, D, H, W); any non-zero byte counts as 1 (`astype(np.bool_)`, :952) ->
-    PackedBits, the bytes np.packbits(volume != 0, axis = class) gives (torch.ops.rsuper.pack_bits, csrc/morph.hip pack_bits_kernel)."""
+    PackedBits, the bytes np.packbits(volume != 0, axis = class) gives (torch.ops.rsuper.pack_bits, csrc/label_bits.hip pack_bits_kernel)."""
     if not isinstance(volume, torch.Tensor) or not volume.is_cuda:
         raise _l.RSuperHipError('pack_bits_device needs a device tensor (no CPU fallback)')
     if volume.dim() == 4:
@@ -182,7 +182,7 @@ class PackedBits:
             self._u8 = unpack_bits_device(self.packed, self.C)
         return self._u8
 
-    # ---- what the report losses read of a volume without inflating it (csrc/morph.hip unpack_bits_sel / plane_any_bits) --------------------------------
+    # ---- what the report losses read of a volume without inflating it (csrc/label_bits.hip unpack_bits_sel / plane_any_bits) --------------------------------
     def _force(self, chs):
         key = tuple(int(c) for c in chs)
         f = _FORCE.get((self.C, key, self.packed.device))

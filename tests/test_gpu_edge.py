@@ -155,6 +155,21 @@ def test_unpack_bits_matches_numpy(C, shape):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('shape', [(3, 5, 1), (4, 2, 2), (17, 1, 1)])
+@pytest.mark.parametrize('C', [5, 9])
+def test_unpack_bits_at_the_smallest_awkward_shapes(C, shape):
+    """V = 15, 16, 17 (below, at and past one 16-byte vector) with a partly filled last byte plane (C = 5: one plane, C = 9: two, the second
+    holding one class): np.unpackbits(packed, axis = class)[:C], bit-exact."""
+    import numpy as np
+    from rsuper_amd.training.dataset import unpack_bits_device
+    P = -(-C // 8)
+    packed = np.random.default_rng(C * 100 + shape[0]).integers(0, 256, (2, P) + shape, dtype=np.uint8)    # padding bits set too: they must not leak
+    want = np.unpackbits(packed, axis=1)[:, :C]
+    got = unpack_bits_device(torch.from_numpy(packed).to(DEV), C).cpu().numpy()
+    assert got.dtype == np.uint8 and got.shape == (2, C) + shape and np.array_equal(got, want)
+
+
+@pytest.mark.gpu
 def test_packed_batch_gives_same_loss():
     """calculate_loss on a batch ingested from bit-packed volumes == on the plain uint8 batch."""
     import argparse, sys, os

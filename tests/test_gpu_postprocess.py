@@ -228,3 +228,18 @@ def test_prediction_deep_case_in_independent_chunks():
     assert torch.equal(label, (exp > 0.5).to(torch.uint8))
     whole = inference_sliding_window(nets[0], img[None, None], args, to_cpu=False).squeeze(0)
     assert not torch.equal(raw, whole)           # windows across the chunk boundary would give other numbers
+
+
+@pytest.mark.parametrize('pair', [((8, 8, 32), (7, 7, 31)), ((8, 7, 31), (7, 8, 32)), ((4, 8, 31), (4, 7, 32))])
+def test_largest_component_ignores_a_diagonal_pair_across_a_tile_corner(pair):
+    """6-connectivity at a corner of the 8 x 8 x 32 labelling tile: two voxels that touch only diagonally are two singletons, so the three-voxel
+    run across the x = 31 | 32 tile face is the largest component."""
+    from rsuper_amd.inference import keep_largest_component
+    m = np.zeros((9, 9, 33), np.uint8)
+    m[pair[0]] = m[pair[1]] = 1
+    m[2, 2, 30:33] = 1
+    want = np.zeros_like(m)
+    want[2, 2, 30:33] = 1
+    ref = R.largest_component(m)
+    assert np.array_equal(ref, want)
+    assert np.array_equal(keep_largest_component(torch.from_numpy(m).to(DEV)).cpu().numpy(), ref)

@@ -302,3 +302,25 @@ def test_more_planes_than_one_launch_group_takes():
         assert kept[p] == r[1] and last_state['iterations'][p] == r[2] and np.array_equal(got[p], r[0]), p
     reads = last_state['reads']
     assert reads[0] == 2 and reads[1] == 1 and reads[2] == 0 and reads[63] == reads[0] and reads[64] == 2 and len(reads) == 65
+
+
+# a voxel and its backward neighbour (dz, dy, dx) on either side of a corner of the 8 x 8 x 32 labelling tile of a (9, 9, 33) volume
+TILE_CORNER_PAIRS = {(-1, -1, -1): ((8, 8, 32), (7, 7, 31)), (-1, 1, 1): ((8, 7, 31), (7, 8, 32)), (0, -1, 1): ((4, 8, 31), (4, 7, 32))}
+
+
+@pytest.mark.parametrize('d', sorted(TILE_CORNER_PAIRS))
+def test_a_diagonal_pair_across_a_tile_corner_is_one_component(d):
+    """26-connectivity at a tile corner: two equal peak voxels that touch only diagonally, in tiles that share no face, are one component of size 2,
+    kept in the first iteration with min_voxels = 2; a lower three-voxel run across the x = 31 | 32 tile face stays out of it."""
+    from rsuper_amd.baselines.pseudo_labels import extract_lesion_candidates, last_state
+    a, b = TILE_CORNER_PAIRS[d]
+    assert tuple(p - q for p, q in zip(b, a)) == d
+    v = np.zeros((9, 9, 33), np.float32)
+    v[a] = v[b] = 0.9
+    v[2, 2, 30:33] = 0.5                                                        # inside the mask (thr = 0.36), not adjacent to the pair
+    want = np.zeros(v.shape, np.uint8)
+    want[a] = want[b] = 1
+    ref = pr.candidates(v, 1, min_voxels=2)
+    assert np.array_equal(ref[0], want) and ref[1:] == (1, 1)
+    mask, kept = extract_lesion_candidates(torch.from_numpy(v).to(DEV), 1, min_voxels=2)
+    assert np.array_equal(mask.cpu().numpy(), ref[0]) and kept == ref[1] and last_state['iterations'] == [ref[2]]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Training from whole CTs (training/dataset/whole_ct.py, dataset/packed.py upload_label, csrc/morph.hip pack_bits_kernel): what the path costs.
+"""Training from whole CTs (training/dataset/whole_ct.py, dataset/packed.py upload_label, csrc/label_bits.hip pack_bits_kernel): what the path costs.
 
     pack / unpack   rsuper_pack_bits next to rsuper_unpack_bits on the same (C, D, H, W) volume, alternated repetition by repetition, device events.
                     Algorithmic bytes of both: C * V one-byte planes + ceil(C / 8) * V packed bytes.  GB/s and the share of the float4-copy rate
