@@ -161,8 +161,16 @@ int rsuper_conv3_igemm_s2(int dtype, int mode, const void* xa, int lda, int Ca, 
  * loss.backward(), train_ddp.py:349).  dy rows [0,Ya) accumulate into dwa (Ya, Ca+Cb, 27), rows [Ya,Ya+Yb) into dwb.
  * dwa/dwb are overwritten.  workspace: splits * 27 * (Ya+Yb) * (Ca+Cb) floats (per-split partial slabs, summed by a
  * reduce kernel -- deterministic, no atomics).  use_tr selects ds_read_b64_tr_b16 operand fetch (bf16). */
-/* Number of voxel-tile splits (= partial slabs in `workspace`) rsuper_conv3_wgrad should be called with for this shape:
- * fills the chip with resident blocks for the kernel configuration the launch will pick.  Returns <= 0 on bad arguments. */
+/* THE dispatch query of rsuper_conv3_wgrad / _wgrad_partial: which kernel a launch runs, in which configuration, over how many slabs.  The library makes
+ * that choice in one function; this query, rsuper_conv3_wgrad_splits and the launches read it, so the workspace and the kernel cannot disagree.
+ *   splits = 0: choose the count;  splits != 0: plan for a workspace of that many slabs (the small-volume kernel runs only on its own count).
+ *   src_flags bit 0: one normalised and one raw x source.  Arguments that describe no launch: RSUPER_ERR_ARG.
+ * plan[0] kernel: 0 tile-streaming, 1 second-generation, 2 small-volume;  plan[1] splits;  plan[2] configuration of the tile-streaming kernel (0: 32 rows x
+ * 27 taps, 1: 64 rows x 9 taps, 2: 64 rows x 27 taps);  plan[3] 32-row groups of dY per block (1 / 2).
+ * The count never depends on use_tr or src_flags.  The answer depends on rsuper_conv3_wgrad2_min_tiles at the time. */
+int rsuper_conv3_wgrad_plan(int dtype, int use_tr, int Ca, int Cb, int Ya, int Yb, int N, int D, int H, int W, int src_flags, int splits, int* plan);
+/* Number of voxel-tile splits (= partial slabs in `workspace`) rsuper_conv3_wgrad should be called with for this shape: plan[1] of
+ * rsuper_conv3_wgrad_plan(..., splits = 0).  Returns <= 0 on bad arguments. */
 int rsuper_conv3_wgrad_splits(int dtype, int Ca, int Cb, int Ya, int Yb, int N, int D, int H, int W);
 
 int rsuper_conv3_wgrad(int dtype, int use_tr,

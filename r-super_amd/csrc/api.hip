@@ -21,6 +21,7 @@ static inline int pack_cols(int mode, int na, int nb) { return mode == 1 ? (nb ?
 static inline bool pack_range_ok(int mode, int na, int nb) { return mode != 1 || nb == 0 || ((nb >> 16) % 32 == 0 && (nb & 0xFFFF) > 0 && (nb >> 16) + (nb & 0xFFFF) <= na); }
 
 #include "igemm_plan.hpp"      // which kernel / block width / statistics rows a 3x3x3 igemm launch gets: igemm_plan, s2_kernel (needs dt_ok, bn_ok)
+#include "wgrad_plan.hpp"      // which kernel / configuration / split count a 3x3x3 weight-gradient launch gets: wgrad_plan (needs dt_ok)
 
 // ---- optimiser: split the tensor list into kernel-argument sized chunks
 template <typename F>
@@ -113,7 +114,7 @@ int rsuper_conv3_pack_weights_batch(int dtype, int n, const int* host_desc, cons
 
 int rsuper_conv3_tiles(int D, int H, int W) { return ((D + 3) / 4) * ((H + 3) / 4) * ((W + 15) / 16); }
 
-int rsuper_conv3_wgrad2_min_tiles(int t) { return rs_wgrad2_min_tiles(t); }
+int rsuper_conv3_wgrad2_min_tiles(int t) { return wgrad2_min_tiles(t); }
 
 int rsuper_conv3_variant(int v) {
     if (v >= 0 && v <= 8 && v != 5) g_variant = v;                   // 5 was the second-generation producer/consumer kernel (measured equal, removed)
@@ -250,13 +251,16 @@ int rsuper_conv3_igemm_split_out(int dtype, int epi, const void* xa, int lda, in
                             exa, elda, eCa, emra, exb, eldb, eCb, emrb, stream, out_split, out_part);
 }
 
+int rsuper_conv3_wgrad_plan(int dtype, int use_tr, int Ca, int Cb, int Ya, int Yb, int N, int D, int H, int W, int src_flags, int splits, int* plan) {
+    const WgradPlan pl = wgrad_plan(dtype, use_tr, Ca, Cb, Ya, Yb, N, D, H, W, src_flags, splits);
+    if (!plan || pl.kernel < 0) return RS_ERR_ARG;
+    plan[0] = pl.kernel; plan[1] = pl.splits; plan[2] = pl.cfg; plan[3] = pl.mt;
+    return RS_OK;
+}
+// The earlier query: a thin reader of the plan (the count never depends on use_tr or the sources; -1 where the arguments describe no launch).
 int rsuper_conv3_wgrad_splits(int dtype, int Ca, int Cb, int Ya, int Yb, int N, int D, int H, int W) {
-    if (!dt_ok(dtype) || Ca <= 0 || Cb < 0 || Ya <= 0 || Yb < 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0) return -1;
-    const int nch = (Ca + 31) / 32 + (Cb + 31) / 32, Mtot = Ya + Yb;
-    // the same predicate the launcher evaluates with the real (Ya, Yb): a fused [conv1 | shortcut] whose first source is not a multiple of 32 rows
-    // does not take the small-volume kernel, so its split count must not be sized for it
-    if (const int sv = rs_wgrad_sv_splits(dtype, Mtot, Ya, nch, N, D, H, W)) return sv;        // small volumes: N x (depth parts per sample)
-    return rs_wgrad_splits(dtype, Mtot, nch, N * rsuper_conv3_tiles(D, H, W));
+    const WgradPlan pl = wgrad_plan(dtype, 1, Ca, Cb, Ya, Yb, N, D, H, W, 0, 0);
+    return pl.kernel < 0 ? -1 : pl.splits;
 }
 
 static int conv3_wgrad_impl(int reduce, int dtype, int use_tr, const void* xa, int lda, int Ca, const float* mra,
@@ -280,7 +284,10 @@ static int conv3_wgrad_impl(int reduce, int dtype, int use_tr, const void* xa, i
     p.ya = {ya, ldya, Ya, nullptr};
     p.yb = {yb, ldyb, Yb > 0 ? Yb : 0, nullptr};
     p.dwa = dwa; p.dwb = dwb; p.ws = workspace; p.N = N; p.D = D; p.H = H; p.W = W; p.splits = splits;
-    return rs_launch_wgrad(p, dtype, use_tr, ST(stream), reduce != 0);
+    const bool mixed = p.xb.C > 0 && (p.xa.mr != nullptr) != (p.xb.mr != nullptr);
+    const WgradPlan pl = wgrad_plan(dtype, use_tr, Ca, p.xb.C, Ya, p.yb.C, N, D, H, W, mixed, splits);
+    if (pl.kernel < 0) return RS_ERR_ARG;
+    return rs_launch_wgrad(p, pl, dtype, use_tr, ST(stream), reduce != 0);
 }
 
 int rsuper_conv3_wgrad(int dtype, int use_tr, const void* xa, int lda, int Ca, const float* mra,

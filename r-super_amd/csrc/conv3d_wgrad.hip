@@ -544,10 +544,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(ReduceBatch b) 
     for (int i = threadIdx.x; i < nc * 27; i += 256) dst[i] = tile[i];
 }
 
-static bool g_skip_reduce = false;                               // set by rs_launch_wgrad for the duration of one launch call
-static void launch_reduce_now(const WgradParams& p, hipStream_t st);
-static void launch_reduce(const WgradParams& p, hipStream_t st) { if (!g_skip_reduce) launch_reduce_now(p, st); }
-static void launch_reduce_now(const WgradParams& p, hipStream_t st) {
+static void launch_reduce(const WgradParams& p, hipStream_t st) {
     const int Mtot = p.ya.C + p.yb.C, Cin = p.xa.C + p.xb.C;
     const size_t elems = (size_t)27 * Mtot * Cin;
     if (p.splits >= 128)
@@ -559,7 +556,7 @@ static void launch_reduce_now(const WgradParams& p, hipStream_t st) {
 }
 
 template <typename T, int MT, int NTAPS, int TR, int NW>
-int launch(const WgradParams& p, hipStream_t st) {
+int launch(const WgradParams& p, hipStream_t st, bool reduce) {
     constexpr int XP = WG<T>::XP;
     constexpr int YP = sizeof(T) == 2 ? (MT == 2 ? 192 : 64) : MT * 32 * (int)sizeof(T) + 16;
     constexpr int HDN = NTAPS == 27 ? TD + 2 : TD;
@@ -584,40 +581,11 @@ int launch(const WgradParams& p, hipStream_t st) {
         (void)t_prev;
     }
 #endif
-    launch_reduce(p, st);
+    if (reduce) launch_reduce(p, st);
     return rs_check_launch();
 }
 
 }  // namespace
-
-// Configuration per launch (measured on MI355X, tools/bench_conv.py):
-//   0: M <= 32           -> 32 rows x 27 taps, 8 waves (four taps per wave), one block per CU
-//   1: M > 32, few tiles -> 64 rows x 9 taps (kd split over blocks), 4 waves, two blocks per CU
-//   2: M > 32, >= 128 tiles (bf16) -> 64 rows x 27 taps, 8 waves, one block per CU: the x halo and the dY tile are staged
-//      once for all 27 taps (2.4x less operand traffic than config 1), seven taps per A fragment
-int rs_wgrad_config(int dtype, int Mtot, int tiles_total) {
-    if (Mtot <= 32) return 0;
-    return (dtype == RS_BF16 && tiles_total >= 128) ? 2 : 1;
-}
-
-// 64-row weight gradients with too few tiles for 64-row blocks of the second-generation kernel (the 64 -> 64 layers at 48^3: 864 tiles / 128 splits) run it
-// as two 32-row blocks per chunk: half the splits, 13.5 tiles per block -- 64 -> 64 @48^3 72.5 -> 67.7 us (tools/bench_conv.py, same box).  RSUPER_WG2_MT1=0: off (A/B).
-bool rs_wgrad2_mt1(int dtype, int Mtot, int tiles_total) {
-    static const int on = getenv("RSUPER_WG2_MT1") ? atoi(getenv("RSUPER_WG2_MT1")) : 1;
-    static const int maxm = getenv("RSUPER_WG2_MT1_MAXM") ? atoi(getenv("RSUPER_WG2_MT1_MAXM")) : 64;                // experiment knobs (tools/wg_mt1_exp.sh)
-    static const int mint = getenv("RSUPER_WG2_MT1_MIN_TILES") ? atoi(getenv("RSUPER_WG2_MT1_MIN_TILES")) : 512;
-    return on && dtype == RS_BF16 && Mtot >= 64 && Mtot <= maxm && (Mtot % 32) == 0 && tiles_total >= mint && tiles_total < 2048;
-}
-
-int rs_wgrad_splits(int dtype, int Mtot, int nch, int tiles_total) {
-    const int cfg = rs_wgrad_config(dtype, Mtot, tiles_total);
-    int gy = cfg == 0 ? 1 : (cfg == 1 ? 3 : 1) * ((Mtot + 63) / 64);
-    if (rs_wgrad2_mt1(dtype, Mtot, tiles_total)) gy = Mtot / 32;  // 32-row blocks on the second-generation kernel (twice the tiles per block, half the slab bytes)
-    const int target = cfg == 1 ? 512 : 256;                     // resident blocks on 256 CUs
-    int s = target / (nch * gy > 0 ? nch * gy : 1);
-    if (s > tiles_total) s = tiles_total;
-    return s < 1 ? 1 : s;
-}
 
 int rs_launch_wgrad_reduce_batch(ReduceBatch& b, hipStream_t st) {
     if (b.n <= 0) return RS_OK;
@@ -637,55 +605,24 @@ int rs_launch_wgrad_reduce_batch(ReduceBatch& b, hipStream_t st) {
     return rs_check_launch();
 }
 
-int rs_wgrad2_min_tiles(int t) {
-    static int v = getenv("RSUPER_WGRAD2_MIN_TILES") ? atoi(getenv("RSUPER_WGRAD2_MIN_TILES")) : 12;
-    if (t >= 0) v = t;
-    return v;
-}
-
 int rs_launch_wgrad_reduce(const WgradParams& p, hipStream_t st) {
-    launch_reduce_now(p, st);
+    launch_reduce(p, st);
     return rs_check_launch();
 }
 
-static int launch_wgrad_impl(const WgradParams& p, int dtype, int use_tr, hipStream_t st);
-// reduce = false: only the partial-slab kernel (the caller launches rs_launch_wgrad_reduce itself, e.g. on another stream)
-int rs_launch_wgrad(const WgradParams& p, int dtype, int use_tr, hipStream_t st, bool reduce) {
-    g_skip_reduce = !reduce;
-    const int rc = launch_wgrad_impl(p, dtype, use_tr, st);
-    g_skip_reduce = false;
-    return rc;
-}
-
-static int launch_wgrad_impl(const WgradParams& p, int dtype, int use_tr, hipStream_t st) {
-    const int Mtot = p.ya.C + p.yb.C;
-    const int tiles_total = p.N * ((p.D + TD - 1) / TD) * ((p.H + TH - 1) / TH) * ((p.W + TW - 1) / TW);
-    const int cfg = rs_wgrad_config(dtype, Mtot, tiles_total);
-    if (dtype == RS_F32) return cfg == 0 ? launch<float, 1, 27, 0, 4>(p, st) : launch<float, 2, 9, 0, 4>(p, st);
-    {   // small volumes (12^3 / 6^3 levels): one depth slab of a sample whole in LDS (conv3d_wgrad_sv.hip); the caller sized `splits` for it
-        const int nch = (p.xa.C + 31) / 32 + (p.xb.C + 31) / 32;
-        const int sv = use_tr ? rs_wgrad_sv_splits(dtype, Mtot, p.ya.C, nch, p.N, p.D, p.H, p.W) : 0;
-        if (sv > 0 && sv == p.splits) {
-            const int rc = rs_launch_wgrad_sv(p, st);
-            if (rc != RS_OK) return rc;
-            launch_reduce(p, st);
-            return rs_check_launch();
-        }
+// The launch of a planned weight gradient (wgrad_plan.hpp decides, nothing here does).  reduce = false: only the partial-slab kernel.
+int rs_launch_wgrad(const WgradParams& p, const WgradPlan& plan, int dtype, int use_tr, hipStream_t st, bool reduce) {
+    int rc = RS_ERR_ARG;
+    switch (plan.kernel) {
+        case RS_WGRAD_SV: rc = rs_launch_wgrad_sv(p, st); break;
+        case RS_WGRAD_2: rc = rs_launch_wgrad2(p, plan.mt, st); break;
+        case RS_WGRAD_TILE:
+            if (dtype == RS_F32) return plan.cfg == 0 ? launch<float, 1, 27, 0, 4>(p, st, reduce) : launch<float, 2, 9, 0, 4>(p, st, reduce);
+            if (plan.cfg == 0) return use_tr ? launch<bf16_t, 1, 27, 1, 8>(p, st, reduce) : launch<bf16_t, 1, 27, 0, 8>(p, st, reduce);
+            if (plan.cfg == 1) return use_tr ? launch<bf16_t, 2, 9, 1, 4>(p, st, reduce) : launch<bf16_t, 2, 9, 0, 4>(p, st, reduce);
+            return use_tr ? launch<bf16_t, 2, 27, 1, 8>(p, st, reduce) : launch<bf16_t, 2, 27, 0, 8>(p, st, reduce);
     }
-    // Second-generation kernel (conv3d_wgrad2.hip: operand re-use across taps, double-buffered tiles) where a block sweeps enough tiles to amortise its
-    // heavier prologue (descriptor / constants tables, two tiles staged before the first MFMA): measured same-box against the kernel below, >= 12 tiles
-    // per block 0.81-0.93x (32 -> 32 @96^3, up4.0, up3.0, up2.0), 6.75 tiles per block 1.02-1.08x (64 -> 64 @48^3, 128 -> 128 @24^3, down1.0)
-    if (use_tr && cfg != 1 && (long)tiles_total >= (long)rs_wgrad2_min_tiles(-1) * p.splits && rs_wgrad2_supported(p, dtype)) {
-        const int rc = rs_launch_wgrad2(p, st);
-        if (rc != RS_OK) return rc;
-        launch_reduce(p, st);
-        return rs_check_launch();
-    }
-    if (dtype == RS_BF16) {
-        // bf16 launches the second-generation kernel above did not take: few tiles per block, the 9-tap configuration, RSUPER_WGRAD_TR=0
-        if (cfg == 0) return use_tr ? launch<bf16_t, 1, 27, 1, 8>(p, st) : launch<bf16_t, 1, 27, 0, 8>(p, st);
-        if (cfg == 1) return use_tr ? launch<bf16_t, 2, 9, 1, 4>(p, st) : launch<bf16_t, 2, 9, 0, 4>(p, st);
-        return use_tr ? launch<bf16_t, 2, 27, 1, 8>(p, st) : launch<bf16_t, 2, 27, 0, 8>(p, st);
-    }
-    return RS_ERR_ARG;
+    if (rc != RS_OK) return rc;
+    if (reduce) launch_reduce(p, st);
+    return rs_check_launch();
 }

@@ -437,22 +437,11 @@ int launch2(const WgradParams& p, hipStream_t st) {
 
 }  // namespace
 
-// bf16; 32-row groups of dY inside one source each (buffer resources are wave-uniform)
-bool rs_wgrad2_supported(const WgradParams& p, int dtype) {
-    static const int off = getenv("RSUPER_WGRAD2") ? atoi(getenv("RSUPER_WGRAD2")) == 0 : 0;
-    if (off || dtype != RS_BF16 || p.N > 32) return false;      // per-sample constants table: 256 B of LDS per sample
-    if (p.yb.C > 0 && (p.ya.C % 32)) return false;
-    if ((p.xa.mr != nullptr) != (p.xb.C > 0 ? p.xb.mr != nullptr : p.xa.mr != nullptr)) return false;   // both sources normalised or both raw, as everywhere
-    return true;
-}
-
-int rs_launch_wgrad2(const WgradParams& p, hipStream_t st) {
-    const int Mtot = p.ya.C + p.yb.C;
+// what the kernel requires of a launch is wgrad2_supported (wgrad_plan.hpp); mt: 32-row groups of dY per block, from the plan
+int rs_launch_wgrad2(const WgradParams& p, int mt, hipStream_t st) {
 #ifndef WG2_BD
 #define WG2_BD 2
 #endif
-    const int tiles = p.N * ((p.D + TD - 1) / TD) * ((p.H + TH - 1) / TH) * ((p.W + TW - 1) / TW);
-    const bool mt1 = Mtot <= 32 || rs_wgrad2_mt1(RS_BF16, Mtot, tiles);
-    if (p.xa.mr) return mt1 ? launch2<1, WG2_BD, true>(p, st) : launch2<2, WG2_BD, true>(p, st);
-    return mt1 ? launch2<1, WG2_BD, false>(p, st) : launch2<2, WG2_BD, false>(p, st);
+    if (p.xa.mr) return mt == 1 ? launch2<1, WG2_BD, true>(p, st) : launch2<2, WG2_BD, true>(p, st);
+    return mt == 1 ? launch2<1, WG2_BD, false>(p, st) : launch2<2, WG2_BD, false>(p, st);
 }

@@ -227,22 +227,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_sv_kernel(WgradParams p, int P, i
 
 }  // namespace
 
-// splits (= N x parts per sample) of the small-volume kernel, 0 when it does not apply: bf16, a slab of at least one plane fits LDS, at most 64 tiles of
-// 4x4x16 voxels in the batch (the levels where the tile-streaming kernels sweep < 4 tiles per block), 32-row groups of dY inside one source each
-int rs_wgrad_sv_splits(int dtype, int Mtot, int Ya, int nch, int N, int D, int H, int W) {
-    static const int off = getenv("RSUPER_WGRAD_SV") ? atoi(getenv("RSUPER_WGRAD_SV")) == 0 : 0;
-    const int w2 = rs_wgrad2_min_tiles(-1);
-    if (off || dtype != RS_BF16 || w2 == 0 || w2 >= (1 << 20)) return 0;      // 0 / "never": the tests force the tile-streaming kernels
-    const long tiles = (long)N * ((D + 3) / 4) * ((H + 3) / 4) * ((W + 15) / 16);
-    if (tiles > 64 || (Ya < Mtot && (Ya % 32))) return 0;
-    // above 6^3 the kernel pays only while the whole launch is small: the wide fused [conv1 | shortcut] of up1.0 (512 rows x 18 input chunks at 12^3 = 288 output
-    // tiles x N x depth parts blocks, each re-staging its slab) measured 180 us here against 120 us on the tile-streaming kernel; 256 -> 256 / 128 -> 2 x 256 at
-    // 12^3 are equal on both, the 6^3 level is 20-25 % faster here (tools/r06_wgsv_exp.sh, profiles/r06_wgsv_exp.txt)
-    static const long max_tiles12 = getenv("RSUPER_WGRAD_SV_MAX") ? atol(getenv("RSUPER_WGRAD_SV_MAX")) : 4096;
-    if ((long)D * H * W > 216 && (long)Mtot * nch > max_tiles12) return 0;
-    const SvGeom g = sv_geometry(N, D, H, W, nch, Mtot);
-    return g.P > 0 ? N * g.P : 0;
-}
+int rs_wgrad_sv_parts(int N, int D, int H, int W, int nch, int Mtot) { return sv_geometry(N, D, H, W, nch, Mtot).P; }
 
 int rs_launch_wgrad_sv(const WgradParams& p, hipStream_t st) {
     const int nch = (p.xa.C + 31) / 32 + (p.xb.C + 31) / 32;

@@ -93,7 +93,15 @@ int rs_launch_pack(const PackParams& q, int dtype, void* out, hipStream_t st);
 // softmax(q k^T * scale) v of a short token sequence (token_attn.hip); d_qkv == nullptr: forward (o, p written), else backward (p, d_o read)
 int rs_token_attn_supported(int L, int Dh);
 int rs_launch_token_attn(const float* qkv, float* o, float* p, const float* d_o, float* d_qkv, int B, int L, int H, int Dh, float scale, hipStream_t st);
-int rs_launch_wgrad(const WgradParams& p, int dtype, int use_tr, hipStream_t st, bool reduce = true);
+// The kernels of the stride-1 3x3x3 weight gradient.  wgrad_plan (wgrad_plan.hpp) is the only place one is chosen; rs_launch_wgrad switches over it.
+enum WgradKernel {
+    RS_WGRAD_TILE = 0,     // tile-streaming kernel (conv3d_wgrad.hip; f32 and bf16), configuration 0 / 1 / 2
+    RS_WGRAD_2 = 1,        // second-generation kernel (conv3d_wgrad2.hip; bf16): operand re-use across taps + double-buffered tiles
+    RS_WGRAD_SV = 2        // small-volume kernel (conv3d_wgrad_sv.hip; bf16): a depth slab of one sample whole in LDS, flat-voxel reduction
+};
+struct WgradPlan { int kernel, splits, cfg, mt; };    // WgradKernel, slabs, configuration of the tile kernel, 32-row groups of dY per block
+// reduce = false: only the partial-slab kernel (the caller launches rs_launch_wgrad_reduce itself, e.g. on another stream)
+int rs_launch_wgrad(const WgradParams& p, const WgradPlan& plan, int dtype, int use_tr, hipStream_t st, bool reduce);
 int rs_launch_wgrad_reduce(const WgradParams& p, hipStream_t st);
 // slab reductions of several weight gradients in ONE launch (the per-layer reduce is a ~10 us launch at the dependent-launch floor, 34 per step)
 #define RS_REDUCE_BATCH_MAX 48
@@ -109,15 +117,11 @@ struct ReduceBatch {
     struct Stats { const float* part; float* out; int N, nblk, C, mode, split; float eps; double cnt; unsigned blk_start; } sj[RS_REDUCE_STATS_MAX];
 };
 int rs_launch_wgrad_reduce_batch(ReduceBatch& b, hipStream_t st);
-bool rs_wgrad2_mt1(int dtype, int Mtot, int tiles_total);
-int rs_wgrad_splits(int dtype, int Mtot, int nch, int tiles_total);
-// small-volume weight gradient (conv3d_wgrad_sv.hip): a depth slab of one sample whole in LDS, flat-voxel reduction; splits = 0: does not apply
-int rs_wgrad_sv_splits(int dtype, int Mtot, int Ya, int nch, int N, int D, int H, int W);
-int rs_launch_wgrad_sv(const WgradParams& p, hipStream_t st);
-// second-generation weight gradient (conv3d_wgrad2.hip): bf16, operand re-use across taps + double-buffered tiles; same slabs, the caller reduces
-bool rs_wgrad2_supported(const WgradParams& p, int dtype);
-int rs_wgrad2_min_tiles(int t);     // tiles per block from which bf16 launches take it (t < 0: query)
-int rs_launch_wgrad2(const WgradParams& p, hipStream_t st);
+// small-volume weight gradient: depth parts per sample of its launch geometry (0: no slab of a whole plane fits LDS); it writes N x parts slabs
+int rs_wgrad_sv_parts(int N, int D, int H, int W, int nch, int Mtot);
+int rs_launch_wgrad_sv(const WgradParams& p, hipStream_t st);         // p.splits != N x parts: RS_ERR_ARG
+// second-generation weight gradient: mt = 32-row groups of dY per block (1 / 2); same slabs as the tile kernel, the caller reduces
+int rs_launch_wgrad2(const WgradParams& p, int mt, hipStream_t st);
 // stride-2 convolution (conv3d_wgrad_s2.hip): p.N/D/H/W = the FULL-resolution grid of x, dY lives on the ((D+1)/2, (H+1)/2, (W+1)/2) grid; xb unused
 int rs_wgrad_s2_splits(int dtype, int Ca, int Mtot, int N, int D, int H, int W);
 int rs_launch_wgrad_s2(const WgradParams& p, int dtype, hipStream_t st);

@@ -29,6 +29,7 @@ _SIGS = {
     'rsuper_conv3_kd_bn': (c_int, [c_int] * 8),
     'rsuper_conv3_set_workspace': (c_int, [P, c_size_t]),
     'rsuper_conv3_workspace_bytes': (c_size_t, []),
+    'rsuper_conv3_wgrad_plan': (c_int, [c_int] * 12 + [P]),
     'rsuper_conv3_wgrad_splits': (c_int, [c_int] * 9),
     'rsuper_conv3_part_rows': (c_int, [c_int] * 9),
     'rsuper_conv3_s2_part_rows': (c_int, [c_int] * 9),
@@ -165,6 +166,8 @@ _SIGS = {
 
 # plan[0] of rsuper_conv3_plan
 IGEMM_CLASSIC, IGEMM_PC, IGEMM_WS, IGEMM_KD, IGEMM_BOX = range(5)
+# plan[0] of rsuper_conv3_wgrad_plan
+WGRAD_TILE, WGRAD_2, WGRAD_SV = range(3)
 
 ERR = {1: 'RSUPER_ERR_ARG', 2: 'RSUPER_ERR_LAUNCH', 3: 'RSUPER_ERR_UNSUPPORTED', 4: 'RSUPER_ERR_NO_DEVICE'}
 

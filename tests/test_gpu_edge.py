@@ -1555,3 +1555,74 @@ def test_persistent_strided_forward_matches_parity_class_kernel():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, 'tools', 'check_s2k.py')], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith('OK'), r.stdout[-2000:] + r.stderr[-2000:]
+
+
+_WGRAD_OPERANDS = {}
+
+
+def _wgrad_operands(S, Ca, Ya):
+    """bf16 x / dY of one sample (random normal, raw sources) on the device and the float64 weight gradient on exactly those operands; computed once per shape."""
+    key = (S, Ca, Ya)
+    if key not in _WGRAD_OPERANDS:
+        x = gc._rng_t(11 + Ca, (1, Ca) + S).bfloat16()
+        dy = gc._rng_t(17 + Ya, (1, Ya) + S).bfloat16()
+        w = torch.zeros((Ya, Ca, 3, 3, 3), dtype=torch.float64, requires_grad=True)
+        F.conv3d(x.double(), w, padding=1).backward(dy.double())
+        _WGRAD_OPERANDS[key] = (gc.to_cl(x.float(), torch.bfloat16), gc.to_cl(dy.float(), torch.bfloat16), w.grad.float())
+    return _WGRAD_OPERANDS[key]
+
+
+# (volume, x channels, dY rows, rsuper_conv3_wgrad2_min_tiles (None: the default), splits the caller passes (0: the chosen count), expected plan[0], [2], [3])
+_WGRAD_PLAN_CASES = [
+    ((8, 8, 16), 32, 32, 1 << 20, 0, 'tile', 0, 1),
+    ((8, 8, 16), 32, 64, 1 << 20, 0, 'tile', 1, 2),
+    ((8, 8, 16), 32, 32, 0, 0, 'wgrad2', 0, 1),             # second-generation kernel, 32-row form
+    ((8, 8, 16), 32, 64, 0, 0, 'tile', 1, 2),               # 4 tiles: the 9-tap configuration, which the second-generation kernel never takes
+    ((16, 32, 64), 32, 64, 0, 0, 'wgrad2', 2, 2),           # 128 tiles: second-generation kernel, 64-row form
+    ((16, 32, 64), 32, 64, 1 << 20, 0, 'tile', 2, 2),
+    ((6, 6, 6), 64, 64, None, 0, 'sv', 1, 1),
+    ((6, 6, 6), 64, 64, None, 1, 'tile', 1, 2),             # a count the small-volume kernel would not choose: a tile-streaming kernel
+]
+
+
+@pytest.mark.parametrize('S,Ca,Ya,thr,splits,kernel,cfg,mt', _WGRAD_PLAN_CASES)
+def test_wgrad_entry_points_agree_on_every_kernel_of_the_plan(S, Ca, Ya, thr, splits, kernel, cfg, mt):
+    """rsuper_conv3_wgrad and rsuper_conv3_wgrad_partial + rsuper_conv3_wgrad_reduce launch from one plan (csrc/wgrad_plan.hpp) and a plain `reduce`
+    argument: on every kernel of the plan both give bit-identical dW, within 1e-4 of max of the float64 gradient on the bf16 operands (f32 accumulation is
+    the only difference: the bound of gpu_checks.check_wgrad_xhat).  8x8x16 has 4 tiles: at the default threshold it is a small-volume launch, so the tile
+    kernel is pinned the way gpu_checks.with_wgrad_classic pins it (threshold "never"), and its 64-row launch is configuration 1 under every threshold, which
+    the second-generation kernel never takes; the 64-row form of that kernel (and configuration 2) needs 128 tiles: 16x32x64."""
+    import ctypes
+    from rsuper_amd.hip import lib
+    L = lib.lib()
+    names = {'tile': lib.WGRAD_TILE, 'wgrad2': lib.WGRAD_2, 'sv': lib.WGRAD_SV}
+    x, dy, ref = _wgrad_operands(S, Ca, Ya)
+    st = torch.cuda.current_stream().cuda_stream
+    old = L.rsuper_conv3_wgrad2_min_tiles(-1)
+    try:
+        if thr is not None:
+            L.rsuper_conv3_wgrad2_min_tiles(thr)
+        plan = (ctypes.c_int * 4)()
+        assert L.rsuper_conv3_wgrad_plan(lib.BF16, 1, Ca, 0, Ya, 0, 1, *S, 0, splits, plan) == 0
+        assert (plan[0], plan[2], plan[3]) == (names[kernel], cfg, mt), tuple(plan)
+        n = plan[1]
+        assert n == (splits or L.rsuper_conv3_wgrad_splits(lib.BF16, Ca, 0, Ya, 0, 1, *S)) and n >= 1
+        src = (x.data_ptr(), Ca, Ca, None, None, 0, 0, None, dy.data_ptr(), Ya, Ya, None, 0, 0)
+        dws = []
+        for two_step in (False, True):
+            dw = torch.full((Ya, Ca, 3, 3, 3), float('nan'), device=DEV)
+            ws = torch.full((n * 27 * Ya * Ca,), float('nan'), device=DEV)
+            if two_step:
+                assert L.rsuper_conv3_wgrad_partial(lib.BF16, 1, *src, ws.data_ptr(), 1, *S, n, st) == 0
+                assert bool(torch.isnan(dw).all())                                # the partial entry leaves dW alone
+                assert L.rsuper_conv3_wgrad_reduce(ws.data_ptr(), n, Ca, Ya, 0, dw.data_ptr(), None, st) == 0
+            else:
+                assert L.rsuper_conv3_wgrad(lib.BF16, 1, *src, dw.data_ptr(), None, ws.data_ptr(), 1, *S, n, st) == 0
+            torch.cuda.synchronize()
+            dws.append(dw.cpu())
+    finally:
+        L.rsuper_conv3_wgrad2_min_tiles(old)
+    assert torch.equal(dws[0], dws[1])
+    e = gc.relerr(dws[1], ref)
+    print(f'wgrad plan {tuple(plan)} S{S} {Ca}->{Ya}: dW vs float64 {e:.2e} (bound 1e-4)')
+    assert e <= 1e-4, e
