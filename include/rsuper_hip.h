@@ -626,6 +626,43 @@ int rsuper_intensity_augment(const float* img, float* out, int B, int D, int H, 
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Models Genesis pre-training -- baselines/model_genesis/utils.py generate_one_pair :206-266 (flips :50, local_pixel_shuffling :76,
+ * nonlinear_transformation :61, image_in_painting :106, image_out_painting :125) and losses_foundation.py model_genesis_loss :667.
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_GENESIS_MAX_BOXES 5
+#define RSUPER_GENESIS_MAX_BLOCK_SIDE 16
+#define RSUPER_GENESIS_MAX_AXIS 169
+/* img [B][D][H][W] f32 -> the pair x, y (two more buffers of that shape; none may alias another).  The reference's (rows, cols, deps) are (D, H, W).
+ * Per sample b, HOST arrays: flags[b] = bit 0 / 1 / 2 the net flip of D / H / W (x and y alike), 3 local pixel shuffling, 4 the non-linear intensity
+ * curve, 5 in-painting, 6 out-painting (5 and 6 exclude each other); nbox[b] <= RSUPER_GENESIS_MAX_BOXES and boxes[b][RSUPER_GENESIS_MAX_BOXES][6] =
+ * (z0, y0, x0, nz, ny, nx) of the painted boxes, inside the volume; seeds[b] = the Philox4x32-10 key of the sample.  DEVICE arrays:
+ * blocks [B][nb][6] (z0, y0, x0, nz, ny, nx), the nb shuffled blocks of every sample in the order they apply, a side at most
+ * RSUPER_GENESIS_MAX_BLOCK_SIDE; perm (optional) the source position of every box position, flattened row-major and concatenated, block k of sample b at
+ * perm_off[b][k] (perm_len entries in all): box.flat[i] = orig_box.flat[perm[i]], where orig is the flipped normalised image, never the partly shuffled
+ * one -- a voxel carries what the last block covering it wrote.  Without perm the device draws perm_k = the stable argsort of the keys
+ * philox(counter (i, k, 2, 0), seed)[0], i = 0 .. n_k - 1 (uniform up to the probability of a tie, about n_k^2 / 2^33).  A block that does not lie inside
+ * the volume, a side outside 1 .. 16, offsets past perm_len and perm entries outside 0 .. n_k - 1 are skipped on the device (the voxels keep orig).
+ * curve [B][2][n] f64: the knots xp (ascending) and fp of np.interp, evaluated in f64 with np.interp's expression (multiply and add unfused) and rounded
+ * to f32 once.  noise: optional [B][D][H][W] f32 field of the painted values in the output frame; without it voxel i takes u = ((r >> 8) + 0.5) * 2^-24
+ * of word i & 3 of philox(counter (i >> 2 low, i >> 2 high, 1, 0), seed).
+ * v = (img - min) / max(max - min, 1e-7f) per sample; y = flip(v); x = flip(v) -> shuffle -> curve -> paint; both leave as v * span + min, in f32 with
+ * IEEE division and unfused multiply-add: bit for bit the reference's values for the same plan.  workspace: device, 8-byte aligned,
+ * rsuper_genesis_workspace_bytes(B, D, H, W, nb) bytes (nb = 0 when no sample shuffles).  rsuper_genesis_launches: kernel launches of the call, per group
+ * of 8 samples 4 when one of them shuffles, else 2.  No float atomics, no memset: bit-reproducible.  An axis above RSUPER_GENESIS_MAX_AXIS, flags outside
+ * 0..127 or with bits 5 and 6, a painted box outside the volume, a missing array or a short workspace -> RSUPER_ERR_ARG. */
+long rsuper_genesis_workspace_bytes(int B, int D, int H, int W, int nb);
+int rsuper_genesis_launches(int B, const int* flags);
+int rsuper_genesis_pair(const float* img, float* x, float* y, int B, int D, int H, int W, const int* flags, int nb, const int* blocks, const int* perm,
+                        const long long* perm_off, long long perm_len, const double* curve, int n, const int* nbox, const int* boxes,
+                        const unsigned long long* seeds, const float* noise, void* workspace, long workspace_bytes, void* stream);
+/* out[0] = mean((r - y)^2) over n f32 elements: per block the f64 sum of the exact squared differences rounded to one f32 partial in `workspace`
+ * (device, rsuper_mse_workspace_bytes(n) bytes), then one block sums the partials in a fixed order -- two launches, no atomics.
+ * rsuper_mse_bwd: dr = g[0] * 2 * (r - y) / n, evaluated in f64 and rounded once (g: the device scalar gradient of out). */
+long rsuper_mse_workspace_bytes(long n);
+int rsuper_mse_fwd(const float* r, const float* y, long n, float* out, void* workspace, long workspace_bytes, void* stream);
+int rsuper_mse_bwd(const float* r, const float* y, const float* g, long n, float* dr, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whole-CT preprocessing and spacing resampling -- predict_abdomenatlas.py preprocess :325-356 (from the clip onward), pad_to_training_size
  * :249-306, unpad_img :311-322, resample_image_with_gpu :718-742.
  * ------------------------------------------------------------------------------------------------ */

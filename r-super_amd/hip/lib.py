@@ -12,6 +12,7 @@ SO_PATH = os.path.join(os.path.dirname(_HERE), 'csrc', 'librsuper_hip.so')
 
 F32, BF16 = 0, 1
 BLUR_MAX_RADIUS = 5        # RSUPER_BLUR_MAX_RADIUS of the header: rsuper_intensity_augment takes 2 * BLUR_MAX_RADIUS + 1 taps per sample
+GENESIS_MAX_BOXES, GENESIS_MAX_BLOCK_SIDE, GENESIS_MAX_AXIS = 5, 16, 169      # RSUPER_GENESIS_* of the header
 _LIB = None
 
 P = c_void_p
@@ -139,6 +140,12 @@ _SIGS = {
     'rsuper_intensity_augment_workspace_bytes': (c_long, [c_int] * 4),
     'rsuper_intensity_augment_launches': (c_int, [c_int, P]),
     'rsuper_intensity_augment': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_long, P]),
+    'rsuper_genesis_workspace_bytes': (c_long, [c_int] * 5),
+    'rsuper_genesis_launches': (c_int, [c_int, P]),
+    'rsuper_genesis_pair': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_longlong, P, c_int, P, P, P, P, P, c_long, P]),
+    'rsuper_mse_workspace_bytes': (c_long, [c_long]),
+    'rsuper_mse_fwd': (c_int, [P, P, c_long, P, P, c_long, P]),
+    'rsuper_mse_bwd': (c_int, [P, P, P, c_long, P, P]),
     'rsuper_surface_codes': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     'rsuper_edt3_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_edt3': (c_int, [P] + [c_int] * 9 + [c_double] * 3 + [P, P, c_long, P]),

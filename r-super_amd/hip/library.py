@@ -35,6 +35,9 @@ report-annotated crops from a whole CT (training/augmentation.py; no derivative)
     torch.ops.rsuper.label_remap(packed, C_in, C_out, nvol, masks, ones) -> remapped packed volumes
 whole-CT label upload (training/dataset/packed.py; no derivative):
     torch.ops.rsuper.pack_bits(volume) -> np.packbits(volume != 0, axis = class) of a one-byte (B, C, ...) volume
+Models Genesis pre-training (baselines/model_genesis/utils.py, training/losses_foundation.py):
+    torch.ops.rsuper.genesis_pair(img, flags, blocks, perm, perm_off, curve, nbox, boxes, seeds, noise, workspace) -> (x, y)      (no derivative)
+    torch.ops.rsuper.mse_loss(result, label) -> mean squared difference                                                       (derivative for result)
 whole-case preprocessing and resampling (inference/preprocess.py, inference/resample.py; no derivative):
     torch.ops.rsuper.ct_normalize(hu, lo, hi, out_shape, offset, workspace) -> (z-scored, zero-padded volume, (mean, std))
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
@@ -228,6 +231,24 @@ def install_intensity_ops(intensity_augment):
     return _install_plain('intensity', (
         ('intensity_augment', '(Tensor img, int[] flags, float[] scalars, int[] radius, float[] taps, int[] seeds, '
          'Tensor? noise=None, Tensor? workspace=None) -> Tensor', intensity_augment),))[0]
+
+
+def install_genesis_ops(genesis_pair):
+    """The pretext-pair operator of baselines/model_genesis (on its first use): the network's input and target have no derivative.  seeds are the 64-bit
+    Philox keys as signed ints (the schema has no unsigned type)."""
+    return _install_plain('genesis', (
+        ('genesis_pair', '(Tensor img, int[] flags, Tensor? blocks, Tensor? perm, Tensor? perm_off, Tensor? curve, int[] nbox, int[] boxes, int[] seeds, '
+         'Tensor? noise=None, Tensor? workspace=None) -> (Tensor, Tensor)', genesis_pair),))[0]
+
+
+_MSE = []
+
+
+def install_mse_op(MseFn):
+    """The voxel-wise MSE of model_genesis_loss (training/losses_foundation.py, on its first use) with its derivative."""
+    if not _MSE:
+        _MSE.append(_register('mse_loss', '(Tensor result, Tensor label) -> Tensor', MseFn))
+    return _MSE[0]
 
 
 def install_preprocess_ops(ct_normalize):

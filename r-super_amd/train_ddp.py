@@ -106,15 +106,16 @@ def train_step(net, ema_net, optimizer, batch, args, classes, step, matcher=None
     volumes, mask, diameters[, weights] already on the device.  Returns the loss dict (device tensors) and the
     pre-clip gradient norm."""
     img = batch['image']
+    genesis = bool(getattr(args, 'model_genesis_pretrain', False))     # batch['label'] is then the pretext target of image (:277-285, :325)
     optimizer.zero_grad(set_to_none=True)
     # the batch-only inputs of the report losses (dilated segment masks, three small host reads) go into the queue AHEAD of the forward pass
     pre = lf.prepare_report_supervision(batch['label'], batch.get('unk_channels'), batch.get('mask'), batch.get('volumes'), batch.get('diameters'),
-                                        classes, args) if PREFETCH_SUPERVISION else None
+                                        classes, args) if (PREFETCH_SUPERVISION and not genesis) else None
     result = net(img)
     loss_all = lf.calculate_loss(model_output=result, label=batch['label'], unk_voxels=batch.get('unk_channels'), args=args,
                                  matcher=matcher, chosen_segment_mask=batch.get('mask'),
                                  tumor_volumes_report=batch.get('volumes'), tumor_diameters=batch.get('diameters'),
-                                 classes=classes, input_tensor=img, class_weights=batch.get('weights'), pre=pre)
+                                 classes=classes, input_tensor=img, class_weights=batch.get('weights'), model_genesis=genesis, pre=pre)
     loss_all['overall'].backward()
     reducer = getattr(net, '_rsuper_reducer', None)
     if reducer is not None:
@@ -245,6 +246,8 @@ def train_epoch(trainLoader, net, ema_net, optimizer, epoch, writer, scaler, arg
     per-epoch TensorBoard scalars."""
     if getattr(args, 'amp', False):
         raise ValueError('MedFormer seems unstable with amp, please use float32 precision')        # train_ddp.py:316
+    if getattr(args, 'hip_graph', False) and getattr(args, 'model_genesis_pretrain', False):
+        raise ValueError('--model_genesis_pretrain draws a new pretext pair on the host every step: it does not run under --hip_graph')
     net.train()
     start = time.time()
     loss_meters = OrderedDict()
@@ -289,6 +292,9 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
     iter_num_per_epoch = 0
     aug_gpu = getattr(args, 'aug_device', 'cpu') == 'gpu'
     intensity_gpu = getattr(args, 'intensity_aug_device', 'cpu') == 'gpu'
+    genesis = bool(getattr(args, 'model_genesis_pretrain', False))
+    if genesis:
+        from .baselines.model_genesis import generate_pair_batch
     if aug_gpu and not packed:
         raise ValueError('--aug_device gpu resamples the bit-packed volumes: the dataset must deliver packed crops (packed=True)')
     on_device = hasattr(trainLoader, 'prefetch_next')      # dataset/whole_ct.py WholeVolumeLoader: the batch is already the device dictionary
@@ -315,6 +321,12 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
             batch = {k: v.to(dev, non_blocking=True) for k, v in batch.items()}
             if intensity_gpu:
                 batch['image'] = intensity_augment_batch(batch['image'])
+        if genesis:
+            # the pretext pair replaces image and label where the reference's dataset makes it: from the final image, after every augmentation
+            # (dataset_abdomenatlas_UFO.py generate_pair); csrc/genesis.hip, at most four launches
+            x, y = generate_pair_batch(batch['image'])
+            assert x.shape == y.shape, 'Image and label must have the same shape, do you apply model genesis in your dataset?'      # :285
+            batch = dict(image=x, label=y)
         img = batch['image']
         step = i + epoch * len(trainLoader)                      # global steps (:306)
         if lf.SANITY_CHECKS and guard is not None:               # the same three asserts (:311-313) as device flags, raised by guard.poll()
@@ -468,6 +480,12 @@ def get_parser(argv=None, config_root=None):
         args.base_lr = lr
     if reports is not None:
         args.reports = reports
+    if args.model_genesis_pretrain:          # :532-536: one output channel, no deep supervision
+        if args.hip_graph:
+            raise ValueError('--model_genesis_pretrain draws a new pretext pair on the host every step: it does not run under --hip_graph')
+        args.aux_loss = False
+        args.classes = 1
+        args.classes_number = 1
     if args.crop_size is not None:
         args.training_size = [args.crop_size] * 3
     # scale / rotate / translate: random_scale_rotate_translate_3d's own defaults where the YAML has none
@@ -571,7 +589,8 @@ def main_worker(proc_idx, ngpus_per_node, fold_idx, args, result_dict=None, trai
         args.num_workers = int((args.num_workers + ngpus_per_node - 1) / ngpus_per_node)
     if torch.cuda.is_available():
         torch.cuda.set_device(proc_idx % torch.cuda.device_count())
-    args.classes = len(trainset.classes)
+    if not getattr(args, 'model_genesis_pretrain', False):   # there args.classes stays 1 (get_parser)
+        args.classes = len(trainset.classes)
     net, ema_net = init_network(args, classes=trainset.classes, old_classes=load_old_classes(args))
     # --hip_graph in a distributed run: the bare module goes to train_epoch, whose GraphedNetwork averages the gradients itself
     model = wrap_ddp(net, proc_idx) if (args.distributed and not getattr(args, 'hip_graph', False)) else net
@@ -602,6 +621,10 @@ def init_network(args, classes=None, old_classes=None):
     src = getattr(args, 'pretrained', None)
     if update and not src and getattr(args, 'resume', False):
         update = False       # a resumed run: `latest` was saved after the surgery and already holds the new-class heads (train_net loads it)
+    if getattr(args, 'model_genesis_pretrain', False):       # :553-556: the one-channel regression network
+        if update:
+            raise ValueError('--model_genesis_pretrain builds a one-channel network: it does not go with --update_output_layer')
+        classes = ['model_genesis']
     c = old_classes if update else classes
     net = get_model(args, pretrain=args.pretrain, classes=c)
     if update:

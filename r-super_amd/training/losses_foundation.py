@@ -674,12 +674,65 @@ def _delesioned(classes):
     return out
 
 
+class _MseLossFn(torch.autograd.Function):
+    """mean((result - label)^2) over all elements (csrc/genesis.hip): fixed-order partials and a finalise forward, one launch backward; the label
+    takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, result, label):
+        if not (result.is_cuda and label.is_cuda):
+            raise _l.RSuperHipError('mse_loss needs device tensors (no CPU fallback)')
+        if result.shape != label.shape or result.numel() == 0:
+            raise ValueError('mse_loss: result %s and label %s must have the same, non-empty shape' % (tuple(result.shape), tuple(label.shape)))
+        r, y = result.contiguous().float(), label.contiguous().float()
+        n = r.numel()
+        out = torch.empty((), device=r.device, dtype=torch.float32)
+        ws = torch.empty((_L().rsuper_mse_workspace_bytes(n),), device=r.device, dtype=torch.uint8)
+        with torch.cuda.device(r.device):
+            _l.check(_L().rsuper_mse_fwd(_ptr(r), _ptr(y), n, _ptr(out), _ptr(ws), ws.numel(), _stream()), 'mse_fwd')
+        ctx.save_for_backward(r, y)
+        ctx.dtype = result.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        r, y = ctx.saved_tensors
+        dr = torch.empty_like(r)
+        g = g.contiguous().float()
+        with torch.cuda.device(r.device):
+            _l.check(_L().rsuper_mse_bwd(_ptr(r), _ptr(y), _ptr(g), r.numel(), _ptr(dr), _stream()), 'mse_bwd')
+        return dr.to(ctx.dtype), None
+
+
+def mse_loss(result, label):
+    """torch.nn.functional.mse_loss(result, label, reduction='mean') on the device, as the dispatcher op torch.ops.rsuper.mse_loss."""
+    if not (result.is_cuda and label.is_cuda):               # the dispatcher's "no CPU kernel" error, as the project's own exception
+        raise _l.RSuperHipError('mse_loss needs device tensors (no CPU fallback)')
+    from ..hip import library as _library
+    return _library.install_mse_op(_MseLossFn)(result, label)
+
+
+def model_genesis_loss(result, label):
+    """model_genesis_loss (:667-674): the voxel-wise MSE between the network's one-channel output and the pretext target.  The target is the float
+    volume generate_pair_batch returns (the reference keeps the label float in this mode, train_ddp.py:260); an integer or boolean label is a
+    segmentation label that never went through the pair: it is refused, not converted."""
+    if isinstance(result, tuple) or isinstance(result, list):
+        raise ValueError('Turn off deep supervision for model genesis pretraining')
+    if not (torch.is_floating_point(result) and torch.is_floating_point(label)):
+        raise NotImplementedError('model genesis: the label must be the float pretext target of the image (baselines.model_genesis.generate_pair_batch); '
+                                  'a %s label is a segmentation label, and the MSE of class masks is not a supported loss' % str(label.dtype))
+    l = mse_loss(result, label)
+    return {'genesis_loss': l, 'overall': l}
+
+
 def calculate_loss(model_output, label, unk_voxels, args, matcher, chosen_segment_mask,
                    tumor_volumes_report, tumor_diameters, classes, input_tensor=None, class_weights=None,
                    model_genesis=False, clip_only=False, report_embeddings=None, dist=None, pre=None):
     """Same contract as the reference (:685-1076): returns {'segmentation', report keys..., 'overall'}."""
-    if model_genesis or clip_only or getattr(args, 'classification_branch', False) or getattr(args, 'multi_ch_tumor', False):
-        raise NotImplementedError('model_genesis / clip_only / classification_branch / multi_ch_tumor are baselines outside '
+    if model_genesis:                                        # :838-839, before anything else
+        return model_genesis_loss(model_output['segmentation'], label)
+    if clip_only or getattr(args, 'classification_branch', False) or getattr(args, 'multi_ch_tumor', False):
+        raise NotImplementedError('clip_only / classification_branch / multi_ch_tumor are baselines outside '
                                   'the accelerated R-Super path (SURVEY.md section 2.1)')
     _l.require_device()
     merged = any(len(v) > 1 for v in lesion_channel_lists(classes).values())
