@@ -663,6 +663,41 @@ int rsuper_mse_fwd(const float* r, const float* y, long n, float* out, void* wor
 int rsuper_mse_bwd(const float* r, const float* y, const float* g, long n, float* dr, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multi-task and CLIP baselines -- model/dim3/medformer.py ClassificationBranch :12-78, training/losses_foundation.py classification_loss
+ * :614-664, training/info_nce.py :63-126.
+ * ------------------------------------------------------------------------------------------------ */
+/* The tail of ClassificationBranch after its extra_layer, one workgroup per sample: reducer Conv3d(160, 64, 1) -> TransformerBlock(dim 64, depth 1,
+ * 4 heads x 16, mlp 320; pre-LayerNorm eps 1e-5, exact erf GELU, residuals) -> mean over the L tokens -> Linear(64, Nc).  All f32.
+ * x [B][L][160] channels-last tokens; weights: HOST array of 15 device pointers, 16-byte aligned, contiguous f32 in torch's [out][in] layout:
+ *   reducer.weight [64][160], reducer.bias, norm1.weight, norm1.bias, to_qkv.weight [192][64], to_out.weight [64][64], to_out.bias, norm2.weight,
+ *   norm2.bias, fc1.weight [320][64], fc1.bias, fc2.weight [64][320], fc2.bias, head.weight [Nc][64], head.bias.
+ * _fwd: one launch, grid B; writes out [B][Nc] and the activations the backward reads into save (device, 16-byte aligned,
+ *   B * rsuper_cls_tail_save_floats(L) floats, any content).
+ * _bwd: two launches.  The first (grid B) reads dout [B][Nc] and save (which it also uses as scratch), writes dx [B][L][160] and the per-sample
+ *   gradient of every parameter into partials (device, 16-byte aligned, rsuper_cls_tail_partial_floats(B, Nc) floats); the second adds the partials
+ *   in sample order into grads: rsuper_cls_tail_param_floats(Nc) floats, the parameters in the order of `weights`, each in its own layout.
+ * No atomics, no memset, every sum in a fixed order: bit-reproducible.  1 <= L <= 64 and 1 <= Nc <= 768 (rsuper_cls_tail_supported, answered on the
+ * host); other sizes -> RSUPER_ERR_UNSUPPORTED; null / misaligned pointers -> RSUPER_ERR_ARG, checked before anything is launched. */
+int rsuper_cls_tail_supported(int L, int Nc);
+long rsuper_cls_tail_save_floats(int L);
+long rsuper_cls_tail_param_floats(int Nc);
+long rsuper_cls_tail_partial_floats(int B, int Nc);
+int rsuper_cls_tail_fwd(const float* x, const void* const* weights, float* out, float* save, int B, int L, int Nc, void* stream);
+int rsuper_cls_tail_bwd(const float* x, const void* const* weights, const float* dout, float* save, float* dx, float* partials, float* grads, int B, int L,
+                        int Nc, void* stream);
+/* classification_loss from presence flags, one launch.  logits [B][Nc] f32; flags_* [B][C] u8 "class c of sample b has a voxel" of the label, the
+ * chosen segment mask and the unknown voxels (mask / unknown may be NULL = none); class_set: bit c = class c is one of the Nc classes of the head, in
+ * class order (C <= 64, popcount == Nc); weights: NULL or [B][Nc] f32.  target = label | mask; an entry with an unknown flag and a zero target counts 0;
+ * loss[0] = sum(weight * BCE-with-logits) / (B * Nc) and dlogits [B][Nc] = its derivative, both evaluated in f64 in a fixed order and rounded once. */
+int rsuper_cls_loss(const float* logits, const uint8_t* flags_label, const uint8_t* flags_mask, const uint8_t* flags_unk, const float* weights, int B, int C,
+                    int Nc, unsigned long long class_set, float* loss, float* dlogits, void* stream);
+/* info_nce with implicit negatives, reduction 'mean', one launch: rows L2-normalised (eps 1e-12), logits = q k^T / temperature, cross-entropy against the
+ * diagonal.  query, key [N][D] f32; loss[0] and dquery, dkey [N][D] = the derivatives, f64 sums in a fixed order, rounded once.  N <= 64
+ * (rsuper_info_nce_supported), else RSUPER_ERR_UNSUPPORTED. */
+int rsuper_info_nce_supported(int N, int D);
+int rsuper_info_nce(const float* query, const float* key, int N, int D, double temperature, float* loss, float* dquery, float* dkey, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whole-CT preprocessing and spacing resampling -- predict_abdomenatlas.py preprocess :325-356 (from the clip onward), pad_to_training_size
  * :249-306, unpad_img :311-322, resample_image_with_gpu :718-742.
  * ------------------------------------------------------------------------------------------------ */

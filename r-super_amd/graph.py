@@ -66,10 +66,18 @@ def _capture_safe_blas():
         pass
 
 
+def _refuse_branches(net, who):
+    """The classification / CLIP branches of MedFormer (multi-task and CLIP baselines) are not captured: their outputs and losses are not among the
+    static buffers of the graphs."""
+    if getattr(net, 'classification_branch', None) is not None or getattr(net, 'clip_branch', None) is not None:
+        raise ValueError(who + ' does not capture the classification / CLIP branches of MedFormer: use the eager train_step')
+
+
 class GraphedTrainStep:
     def __init__(self, net, ema_net, optimizer, args, classes, warmup=3):
         if not isinstance(optimizer, FusedAdamWEMA) or len(optimizer.param_groups) != 1:
             raise ValueError('GraphedTrainStep needs the fused AdamW+EMA optimiser with one parameter group')
+        _refuse_branches(net, 'GraphedTrainStep')
         if getattr(net, '_rsuper_reducer', None) is not None or hasattr(net, 'module'):
             raise ValueError('data-parallel modules take the eager step (the gradient exchange is not captured)')
         if float(getattr(args, 'report_volume_loss_basic', 0.0)) > 0:
@@ -330,6 +338,7 @@ class GraphedNetwork:
         host no longer enqueues the network's launches one by one); parameters are broadcast from rank 0 like DDP does at construction."""
         if getattr(net, '_rsuper_reducer', None) is not None or hasattr(net, 'module'):
             raise ValueError('GraphedNetwork takes the bare module (it exchanges the gradients itself when torch.distributed is initialised)')
+        _refuse_branches(net, 'GraphedNetwork')
         import torch.distributed as dist
         self.net, self.warmup = net, int(warmup)
         self.group = process_group

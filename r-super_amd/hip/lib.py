@@ -146,6 +146,15 @@ _SIGS = {
     'rsuper_mse_workspace_bytes': (c_long, [c_long]),
     'rsuper_mse_fwd': (c_int, [P, P, c_long, P, P, c_long, P]),
     'rsuper_mse_bwd': (c_int, [P, P, P, c_long, P, P]),
+    'rsuper_cls_tail_supported': (c_int, [c_int, c_int]),
+    'rsuper_cls_tail_save_floats': (c_long, [c_int]),
+    'rsuper_cls_tail_param_floats': (c_long, [c_int]),
+    'rsuper_cls_tail_partial_floats': (c_long, [c_int, c_int]),
+    'rsuper_cls_tail_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    'rsuper_cls_tail_bwd': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    'rsuper_cls_loss': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_ulonglong, P, P, P]),
+    'rsuper_info_nce_supported': (c_int, [c_int, c_int]),
+    'rsuper_info_nce': (c_int, [P, P, c_int, c_int, c_double, P, P, P, P]),
     'rsuper_surface_codes': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     'rsuper_edt3_workspace_bytes': (c_long, [c_int, c_int, c_int]),
     'rsuper_edt3': (c_int, [P] + [c_int] * 9 + [c_double] * 3 + [P, P, c_long, P]),

@@ -38,6 +38,10 @@ whole-CT label upload (training/dataset/packed.py; no derivative):
 Models Genesis pre-training (baselines/model_genesis/utils.py, training/losses_foundation.py):
     torch.ops.rsuper.genesis_pair(img, flags, blocks, perm, perm_off, curve, nbox, boxes, seeds, noise, workspace) -> (x, y)      (no derivative)
     torch.ops.rsuper.mse_loss(result, label) -> mean squared difference                                                       (derivative for result)
+multi-task and CLIP baselines (model/dim3/medformer.py ClassificationBranch, training/losses_foundation.py, training/info_nce.py):
+    torch.ops.rsuper.cls_tail(x, 15 parameters) -> (B, Nc) outputs of the branch tail                                         (derivative for all 16)
+    torch.ops.rsuper.classification_loss(logits, flags_label, flags_mask, flags_unk, weights, class_set) -> loss             (derivative for logits)
+    torch.ops.rsuper.info_nce(query, positive_key, temperature) -> loss                                                      (derivative for both)
 whole-case preprocessing and resampling (inference/preprocess.py, inference/resample.py; no derivative):
     torch.ops.rsuper.ct_normalize(hu, lo, hi, out_shape, offset, workspace) -> (z-scored, zero-padded volume, (mean, std))
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
@@ -139,6 +143,11 @@ def install():
         ('TokenAttnFn', 'token_attention', '(Tensor qkv, int heads, float scale) -> Tensor', None, None),
         ('ChannelNormFn', 'channel_norm', '(Tensor x, float eps, bool relu) -> Tensor', None, None),
         ('DepthwiseConvFn', 'depthwise_conv3', '(Tensor x, Tensor w) -> Tensor', None, None),
+        ('ClsTailFn', 'cls_tail', '(Tensor x, Tensor reducer_w, Tensor reducer_b, Tensor norm1_w, Tensor norm1_b, Tensor qkv_w, Tensor out_w, Tensor out_b, '
+         'Tensor norm2_w, Tensor norm2_b, Tensor fc1_w, Tensor fc1_b, Tensor fc2_w, Tensor fc2_b, Tensor head_w, Tensor head_b) -> Tensor', None, None),
+        ('InfoNceFn', 'info_nce', '(Tensor query, Tensor positive_key, float temperature) -> Tensor', None, None),
+        ('ClsLossFn', 'classification_loss', '(Tensor logits, Tensor flags_label, Tensor? flags_mask, Tensor? flags_unk, Tensor? weights, int class_set) '
+         '-> Tensor', None, None),
     ]
     for cls, name, schema, to_fn, adapt in reg:
         Fn = getattr(_ops, cls)

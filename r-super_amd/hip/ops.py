@@ -1518,6 +1518,119 @@ def pointwise_supported(x, w):
             and (x.numel() // x.shape[-1] + 1) * max(w.shape[0], w.shape[1]) * 4 < (1 << 32))
 
 
+# ------------------------------------------------------------------------------------------------ multi-task / CLIP baselines
+CLS_TAIL_WEIGHTS = 15      # reducer w, b; norm1 w, b; to_qkv w; to_out w, b; norm2 w, b; fc1 w, b; fc2 w, b; head w, b (include/rsuper_hip.h)
+
+
+def cls_tail_supported(L, Nc):
+    """Sizes the fused tail of ClassificationBranch takes (1 <= L <= 64 tokens, 1 <= Nc <= 768 outputs); answered on the host."""
+    return bool(_l.lib().rsuper_cls_tail_supported(int(L), int(Nc)))
+
+
+def _weight_array(ws):
+    return (ctypes.c_void_p * CLS_TAIL_WEIGHTS)(*[w.data_ptr() for w in ws])
+
+
+class ClsTailFn(torch.autograd.Function):
+    """reducer -> TransformerBlock(64, depth 1, 4 x 16, mlp 320) -> token mean -> head of ClassificationBranch (model/dim3/medformer.py) on
+    csrc/cls_branch.hip: one launch forward (one workgroup per sample), two backward (per-sample partials, then their sum in sample order).
+    x (B, L, 160) f32 channels-last tokens, then the 15 parameters in the order of include/rsuper_hip.h; returns (B, Nc) f32."""
+
+    @staticmethod
+    def forward(ctx, x, *ws):
+        if len(ws) != CLS_TAIL_WEIGHTS:
+            raise ValueError('cls_tail takes x and %d parameter tensors, got %d' % (CLS_TAIL_WEIGHTS, len(ws)))
+        if not (x.is_cuda and all(w.is_cuda for w in ws)):
+            raise _l.RSuperHipError('cls_tail needs device tensors (no CPU fallback)')
+        if x.dim() != 3 or x.shape[-1] != 160 or x.dtype != torch.float32 or any(w.dtype != torch.float32 for w in ws):
+            raise ValueError('cls_tail: x must be (B, L, 160) f32 and the parameters f32, got %s %s' % (tuple(x.shape), x.dtype))
+        shapes = [(64, 160), (64,), (64,), (64,), (192, 64), (64, 64), (64,), (64,), (64,), (320, 64), (320,), (64, 320), (64,)]
+        Nc = ws[13].shape[0]
+        if [tuple(w.shape) for w in ws] != shapes + [(Nc, 64), (Nc,)]:
+            raise ValueError('cls_tail: parameter shapes %s do not belong to ClassificationBranch' % ([tuple(w.shape) for w in ws],))
+        B, L = x.shape[:2]
+        if not cls_tail_supported(L, Nc):
+            raise _l.RSuperHipError('cls_tail: L = %d tokens, Nc = %d outputs is outside the fused kernel (1..64, 1..768)' % (L, Nc))
+        x = x.contiguous()
+        ws = tuple(w.detach().contiguous() for w in ws)
+        out = torch.empty((B, Nc), device=x.device, dtype=torch.float32)
+        save = torch.empty((B * _L().rsuper_cls_tail_save_floats(L),), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _l.check(_L().rsuper_cls_tail_fwd(_ptr(x), _weight_array(ws), _ptr(out), _ptr(save), B, L, Nc, _stream()), 'cls_tail_fwd')
+        ctx.save_for_backward(x, save, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, save, *ws = ctx.saved_tensors
+        B, L = x.shape[:2]
+        Nc = ws[13].shape[0]
+        dout = dout.contiguous().float()
+        dx = torch.empty_like(x)
+        part = torch.empty((_L().rsuper_cls_tail_partial_floats(B, Nc),), device=x.device, dtype=torch.float32)
+        grads = torch.empty((_L().rsuper_cls_tail_param_floats(Nc),), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _l.check(_L().rsuper_cls_tail_bwd(_ptr(x), _weight_array(ws), _ptr(dout), _ptr(save), _ptr(dx), _ptr(part), _ptr(grads), B, L, Nc, _stream()),
+                     'cls_tail_bwd')
+        out, off = [], 0
+        for w in ws:
+            out.append(grads[off:off + w.numel()].view(w.shape))
+            off += w.numel()
+        return (dx, *out)
+
+
+class InfoNceFn(torch.autograd.Function):
+    """info_nce(query, positive_key) with implicit negatives, reduction 'mean' (training/info_nce.py) on csrc/cls_branch.hip: ONE launch computes the
+    value and both gradients; the backward scales them by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, query, key, temperature):
+        if not (query.is_cuda and key.is_cuda):
+            raise _l.RSuperHipError('info_nce needs device tensors (no CPU fallback)')
+        q, k = query.contiguous().float(), key.contiguous().float()
+        N, D = q.shape
+        if not _l.lib().rsuper_info_nce_supported(N, D):
+            raise _l.RSuperHipError('info_nce: %d samples is outside the kernel (1..64 per rank)' % N)
+        loss = torch.empty((), device=q.device, dtype=torch.float32)
+        dq, dk = torch.empty_like(q), torch.empty_like(k)
+        with torch.cuda.device(q.device):
+            _l.check(_L().rsuper_info_nce(_ptr(q), _ptr(k), N, D, float(temperature), _ptr(loss), _ptr(dq), _ptr(dk), _stream()), 'info_nce')
+        ctx.save_for_backward(dq, dk)
+        ctx.dtypes = (query.dtype, key.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, dk = ctx.saved_tensors
+        return (dq * g).to(ctx.dtypes[0]), (dk * g).to(ctx.dtypes[1]), None
+
+
+class ClsLossFn(torch.autograd.Function):
+    """classification_loss from the presence flags of label / segment mask / unknown voxels (training/losses_foundation.py): ONE launch computes the
+    scalar and d logits (csrc/cls_branch.hip, f64 in a fixed order); the backward scales d logits by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, flags_label, flags_mask, flags_unk, weights, class_set):
+        if not logits.is_cuda:
+            raise _l.RSuperHipError('classification_loss needs device tensors (no CPU fallback)')
+        x = logits.contiguous().float()
+        B, Nc = x.shape
+        C = flags_label.numel() // B
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _l.check(_L().rsuper_cls_loss(_ptr(x), _ptr(flags_label), _ptr(flags_mask), _ptr(flags_unk), _ptr(weights), B, C, Nc, int(class_set) & 0xFFFFFFFFFFFFFFFF,
+                                          _ptr(loss), _ptr(dx), _stream()), 'cls_loss')
+        ctx.save_for_backward(dx)
+        ctx.dtype = logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dx, = ctx.saved_tensors
+        return (dx * g).to(ctx.dtype), None, None, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------ dispatcher registration
 # every *Fn above becomes the torch.library op rsuper::<name> (schema + CUDA kernel + autograd formula); `XFn.apply` keeps working
 from . import library as _library   # noqa: E402

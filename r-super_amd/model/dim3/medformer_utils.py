@@ -137,13 +137,14 @@ class _LinearFn(torch.autograd.Function):
     on 256 CUs, 186 us for a 128 x 27648 x 512 product (3.4 ms per MedFormer step over all such layers); split 16-way it takes ~35 us."""
 
     @staticmethod
-    def forward(ctx, x, w, b, res=None):
-        """res: a tensor of the output's shape added to it (identity shortcut) -- in the GEMM's epilogue on the HIP path; its gradient is dy."""
+    def forward(ctx, x, w, b, res=None, compute=None):
+        """res: a tensor of the output's shape added to it (identity shortcut) -- in the GEMM's epilogue on the HIP path; its gradient is dy.
+        compute: MFMA operand type of the HIP GEMMs of this call (None: the module-wide GEMM_COMPUTE of the running MedFormer)."""
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         ctx.has_res = res is not None
         ctx.hip = HIP_POINTWISE and x.numel() // x.shape[-1] >= HIP_POINTWISE_MIN_ROWS and ops.pointwise_supported(x, w)
-        ctx.compute = GEMM_COMPUTE
+        ctx.compute = GEMM_COMPUTE if compute is None else compute
         if ctx.hip:          # csrc/pointwise.hip: MFMA GEMM straight from the row-major rows (no library call, no staging copies)
             wc = w.contiguous()
             r2 = None if res is None else res.reshape(-1, w.shape[0]).contiguous()
@@ -167,7 +168,7 @@ class _LinearFn(torch.autograd.Function):
         if ctx.hip and HIP_POINTWISE_WGRAD and ctx.needs_input_grad[1]:
             # csrc/pointwise.hip: dW and db from one pass over dy and x (slabs of the rows, added in slab order)
             dw, db = ops.pointwise_wgrad(dy2.contiguous(), x2.contiguous(), want_db, ctx.compute)
-            return dx, dw, db, (dy if ctx.has_res else None)
+            return dx, dw, db, (dy if ctx.has_res else None), None
         if ctx.needs_input_grad[1]:
             rows = x2.shape[0]
             slabs = next((s for s in (32, 16, 8, 4) if rows % s == 0 and rows // s >= SPLITK_MIN_SLAB), 0) if rows >= SPLITK_MIN_ROWS else 0
@@ -187,7 +188,7 @@ class _LinearFn(torch.autograd.Function):
                     db = torch.mm(_ones_row(dy2.shape[0], dy2.device), dy2).reshape(-1)
             else:
                 db = dy2.sum(0)
-        return dx, dw, db, (dy if ctx.has_res else None)
+        return dx, dw, db, (dy if ctx.has_res else None), None
 
 
 _ONES = {}
@@ -201,13 +202,14 @@ def _ones_row(n, device):
     return _ONES[k]
 
 
-def linear(x, w, b=None, res=None):
-    """F.linear(x, w, b) [+ res]: the shortcut addition rides in the HIP GEMM's epilogue (RSUPER_MF_FUSE_RES=0: a separate add, A/B)."""
+def linear(x, w, b=None, res=None, compute=None):
+    """F.linear(x, w, b) [+ res]: the shortcut addition rides in the HIP GEMM's epilogue (RSUPER_MF_FUSE_RES=0: a separate add, A/B).
+    compute: operand type of the HIP GEMM for this call (None: GEMM_COMPUTE)."""
     rows = x.numel() // x.shape[-1]
     if res is not None and not FUSE_RESIDUAL:
-        return linear(x, w, b) + res
+        return linear(x, w, b, None, compute) + res
     if HIP_POINTWISE and rows >= HIP_POINTWISE_MIN_ROWS and ops.pointwise_supported(x, w):
-        return _LinearFn.apply(x, w, b, res)
+        return _LinearFn.apply(x, w, b, res, compute)
     if HIP_POINTWISE and PAD_OUT_CHANNELS and res is None and rows >= HIP_POINTWISE_MIN_ROWS and w.shape[0] % 4 and w.shape[1] % 4 == 0 and x.is_cuda \
             and x.dtype == torch.float32:
         # an output-channel count that is not a multiple of 4 (the 26-class deep-supervision head, medformer.py:190-194): zero rows pad the weight to the next
@@ -216,14 +218,14 @@ def linear(x, w, b=None, res=None):
         wp = torch.cat([w, w.new_zeros((padn, w.shape[1]))], 0)
         bp = None if b is None else torch.cat([b, b.new_zeros(padn)])
         if ops.pointwise_supported(x, wp):
-            return _LinearFn.apply(x, wp, bp, None)[..., :n]
+            return _LinearFn.apply(x, wp, bp, None, compute)[..., :n]
     if x.dtype == torch.float32 and (rows >= SPLITK_MIN_ROWS or (gemm_library.active and max(rows, w.shape[0], w.shape[1]) >= LT_MIN_K)):
-        return _LinearFn.apply(x, w, b, res)
+        return _LinearFn.apply(x, w, b, res, compute)
     y = F.linear(x, w, b)
     return y if res is None else y + res
 
 
-def pointwise(x, conv, res=None):
+def pointwise(x, conv, res=None, compute=None):
     """Conv3d(k=1) as a GEMM over the channel axis (csrc/pointwise.hip, forward and both gradients; library GEMMs below 32 rows / for channel
     counts that are not multiples of 4); fp32 storage unless GEMM_DTYPE says bf16 (opt-in experiment).  res: shortcut added to the output."""
     w = conv.weight.reshape(conv.weight.shape[0], conv.weight.shape[1])
@@ -231,7 +233,7 @@ def pointwise(x, conv, res=None):
         y = F.linear(x.to(GEMM_DTYPE), w.to(GEMM_DTYPE)).float()
         y = y if conv.bias is None else y + conv.bias
         return y if res is None else y + res
-    return linear(x, w, conv.bias, res)
+    return linear(x, w, conv.bias, res, compute)
 
 
 def depthwise(x, conv):
@@ -460,8 +462,8 @@ class _PreNorm(nn.Module):
         self.norm = nn.LayerNorm(dim)
         self.fn = fn
 
-    def forward(self, x, res=None):
-        return self.fn(self.norm(x), res)
+    def forward(self, x, res=None, compute=None):
+        return self.fn(self.norm(x), res, compute)
 
 
 class _TokenAttention(nn.Module):
@@ -471,10 +473,10 @@ class _TokenAttention(nn.Module):
         self.to_qkv = nn.Linear(dim, 3 * heads * dim_head, bias=False)
         self.to_out = nn.Linear(heads * dim_head, dim)
 
-    def forward(self, x, res=None):
+    def forward(self, x, res=None, compute=None):
         B, L, _ = x.shape
         # projections through linear(): csrc/pointwise.hip (162 token rows: reduction split over the waves), shortcut in the epilogue
-        qkv = linear(x, self.to_qkv.weight)
+        qkv = linear(x, self.to_qkv.weight, compute=compute)
         if HIP_TOKEN_ATTN and qkv.is_cuda and ops.token_attn_supported(L, qkv.shape[-1] // (3 * self.heads)):
             # score / soft-max / mixing in one launch per direction, no transposing copies (csrc/token_attn.hip)
             o = ops.TokenAttnFn.apply(qkv, self.heads, self.scale)
@@ -482,7 +484,7 @@ class _TokenAttention(nn.Module):
             q, k, v = (t.reshape(B, L, self.heads, -1).transpose(1, 2) for t in qkv.chunk(3, -1))
             att = F.softmax(torch.matmul(q, k.transpose(-1, -2)) * self.scale, -1)
             o = torch.matmul(att, v).transpose(1, 2).reshape(B, L, -1)
-        return linear(o, self.to_out.weight, self.to_out.bias, res)
+        return linear(o, self.to_out.weight, self.to_out.bias, res, compute)
 
 
 class _Mlp(nn.Module):
@@ -490,8 +492,8 @@ class _Mlp(nn.Module):
         super().__init__()
         self.fc1, self.fc2 = nn.Linear(dim, hidden), nn.Linear(hidden, dim)
 
-    def forward(self, x, res=None):
-        return linear(F.gelu(linear(x, self.fc1.weight, self.fc1.bias)), self.fc2.weight, self.fc2.bias, res)
+    def forward(self, x, res=None, compute=None):
+        return linear(F.gelu(linear(x, self.fc1.weight, self.fc1.bias, compute=compute)), self.fc2.weight, self.fc2.bias, res, compute)
 
 
 class TransformerBlock(nn.Module):
@@ -502,10 +504,11 @@ class TransformerBlock(nn.Module):
         self.layers = nn.ModuleList(nn.ModuleList([_PreNorm(dim, _TokenAttention(dim, heads, dim_head)), _PreNorm(dim, _Mlp(dim, mlp_dim))])
                                     for _ in range(depth))
 
-    def forward(self, x):
+    def forward(self, x, compute=None):
+        """compute: operand type of the block's HIP GEMMs (None: GEMM_COMPUTE)."""
         for attn, ffn in self.layers:
-            x = attn(x, x)                        # `attn(x) + x`, `ffn(x) + x`: the residual rides in the output projection's epilogue
-            x = ffn(x, x)
+            x = attn(x, x, compute)               # `attn(x) + x`, `ffn(x) + x`: the residual rides in the output projection's epilogue
+            x = ffn(x, x, compute)
         return x
 
 

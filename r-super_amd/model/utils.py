@@ -15,11 +15,19 @@ def get_model(args, pretrain=False, classes=None, classes_cls=None):
         if pretrain:
             raise ValueError('No pretrain model available')
         from .dim3.medformer import MedFormer
+        # model/utils.py:100-106: the classification head's classes are the background / lesion / pnet / cyst / pdac entries unless given
+        class_list_cls = classes_cls
+        if classes_cls is None and classes is not None:
+            class_list_cls = [c for c in classes if any(p in c for p in ('background', 'lesion', 'pnet', 'cyst', 'pdac'))]
+        if getattr(args, 'classification_branch', False) and class_list_cls is None:
+            raise NotImplementedError('classification_branch needs the class list (classes or classes_cls) to size its head; '
+                                      'the reference fails here with TypeError on len(None)')
         n_cls = args.classes if classes is None else len(classes)
         return MedFormer(args.in_chan, n_cls, args.base_chan, map_size=args.map_size, conv_block=args.conv_block, conv_num=args.conv_num,
                          trans_num=args.trans_num, num_heads=args.num_heads, fusion_depth=args.fusion_depth, fusion_dim=args.fusion_dim,
                          fusion_heads=args.fusion_heads, expansion=args.expansion, attn_drop=args.attn_drop, proj_drop=args.proj_drop,
                          proj_type=args.proj_type, norm=args.norm, act=args.act, kernel_size=args.kernel_size, scale=args.down_scale,
                          aux_loss=args.aux_loss, classification_branch=getattr(args, 'classification_branch', False),
+                         class_list_seg=classes, class_list_cls=class_list_cls, clip_branch=bool(getattr(args, 'clip_loss', False)),
                          compute_dtype=getattr(args, 'compute_dtype', None))     # like the reference, the YAML's chan_num is NOT passed
     raise NotImplementedError(f'model {args.model!r} is outside the accelerated hot path (unet / resunet / medformer)')

@@ -107,15 +107,19 @@ def train_step(net, ema_net, optimizer, batch, args, classes, step, matcher=None
     pre-clip gradient norm."""
     img = batch['image']
     genesis = bool(getattr(args, 'model_genesis_pretrain', False))     # batch['label'] is then the pretext target of image (:277-285, :325)
+    clip = bool(getattr(args, 'clip_pretrain', False))                 # CLIP baseline: only the contrastive loss of the CLIP branch (:326-327)
+    if clip and batch.get('clip_embedding') is None:
+        raise ValueError("--clip_pretrain: the batch has no 'clip_embedding' (the report embedding of every sample, (B, clip_feats))")
     optimizer.zero_grad(set_to_none=True)
     # the batch-only inputs of the report losses (dilated segment masks, three small host reads) go into the queue AHEAD of the forward pass
     pre = lf.prepare_report_supervision(batch['label'], batch.get('unk_channels'), batch.get('mask'), batch.get('volumes'), batch.get('diameters'),
-                                        classes, args) if (PREFETCH_SUPERVISION and not genesis) else None
+                                        classes, args) if (PREFETCH_SUPERVISION and not genesis and not clip) else None
     result = net(img)
     loss_all = lf.calculate_loss(model_output=result, label=batch['label'], unk_voxels=batch.get('unk_channels'), args=args,
                                  matcher=matcher, chosen_segment_mask=batch.get('mask'),
                                  tumor_volumes_report=batch.get('volumes'), tumor_diameters=batch.get('diameters'),
-                                 classes=classes, input_tensor=img, class_weights=batch.get('weights'), model_genesis=genesis, pre=pre)
+                                 classes=classes, input_tensor=img, class_weights=batch.get('weights'), model_genesis=genesis, pre=pre,
+                                 clip_only=clip, report_embeddings=batch.get('clip_embedding') if clip else None, dist=torch.distributed if clip else None)
     loss_all['overall'].backward()
     reducer = getattr(net, '_rsuper_reducer', None)
     if reducer is not None:
@@ -306,6 +310,7 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
                      volumes=inputs['volumes'].float(), mask=inputs['mask'], diameters=inputs['diameters'].float())
         if 'weights' in inputs:
             batch['weights'] = inputs['weights'].float()
+        clip_embedding = inputs.get('clip_embedding') if hasattr(inputs, 'get') else None      # whatever the loader provides (--clip_pretrain)
         if on_device:   # cut at training_size by DeviceCropper, its affine branch included: the spatial augmentation must not run again
             batch['image'] = intensity_augment_batch(batch['image'])
         elif packed:      # bit-packed label volumes cross PCIe as stored and are inflated on the device (dataset/packed.py)
@@ -327,6 +332,8 @@ def _train_epoch_loop(trainLoader, net, ema_net, optimizer, epoch, writer, args,
             x, y = generate_pair_batch(batch['image'])
             assert x.shape == y.shape, 'Image and label must have the same shape, do you apply model genesis in your dataset?'      # :285
             batch = dict(image=x, label=y)
+        if clip_embedding is not None:
+            batch['clip_embedding'] = clip_embedding.to(dev, non_blocking=True).float()
         img = batch['image']
         step = i + epoch * len(trainLoader)                      # global steps (:306)
         if lf.SANITY_CHECKS and guard is not None:               # the same three asserts (:311-313) as device flags, raised by guard.poll()
@@ -486,6 +493,12 @@ def get_parser(argv=None, config_root=None):
         args.aux_loss = False
         args.classes = 1
         args.classes_number = 1
+    if args.clip_pretrain:                   # :538-541: the CLIP branch and its loss; no deep supervision, no validation (train_net)
+        if args.hip_graph:
+            raise ValueError('--clip_pretrain trains the CLIP branch, which the graph wrappers do not capture: it does not run under --hip_graph')
+        args.clip_loss = True
+        args.load_clip = True
+        args.aux_loss = False
     if args.crop_size is not None:
         args.training_size = [args.crop_size] * 3
     # scale / rotate / translate: random_scale_rotate_translate_3d's own defaults where the YAML has none

@@ -633,6 +633,8 @@ def _calculate_loss_merged(model_output, label, unk_voxels, args, matcher, chose
     rw = float(args.report_volume_loss_basic)
     a_seg = copy.copy(args)
     a_seg.report_volume_loss_basic = 0.0
+    cls_on = bool(getattr(args, 'classification_branch', False))
+    a_seg.classification_branch = False                     # the classification term is added once, below, from the unmerged channels (:885-887)
     seg = calculate_loss(model_output, label, unk_voxels, a_seg, matcher, chosen_segment_mask, tumor_volumes_report, tumor_diameters,
                          _delesioned(classes), input_tensor, class_weights)
     loss = {'segmentation': seg['segmentation']}
@@ -649,6 +651,7 @@ def _calculate_loss_merged(model_output, label, unk_voxels, args, matcher, chose
             cw = merge_lesion_channels(class_weights.reshape(class_weights.shape[0], -1).float(), classes)[0]
         a_rep = copy.copy(args)
         a_rep.seg_loss = 0.0
+        a_rep.classification_branch = False
         rep = calculate_loss({'segmentation': heads if deep else heads[0]}, lab, unk, a_rep, matcher, msk, tumor_volumes_report,
                              tumor_diameters, names, input_tensor, cw)
         for k, v in rep.items():
@@ -656,6 +659,10 @@ def _calculate_loss_merged(model_output, label, unk_voxels, args, matcher, chose
                 loss[k] = v
     else:
         loss['report'] = seg['report']
+    if cls_on:
+        if class_weights is not None and torch.equal(class_weights, torch.ones_like(class_weights)):     # :876-877
+            class_weights = None
+        loss['classification'] = classification_loss(model_output['classification'], label, unk_voxels, args, chosen_segment_mask, classes, class_weights)
     overall = None
     for k in list(loss.keys()):
         overall = loss[k] if overall is None else overall + loss[k]
@@ -725,16 +732,74 @@ def model_genesis_loss(result, label):
     return {'genesis_loss': l, 'overall': l}
 
 
+def _class_flags(v):
+    """(B * C,) uint8 "class c of sample b has a voxel": from the packed bytes of a bit-packed volume, else one reduction over the planes of a tensor."""
+    if _is_packed(v):
+        return v.class_flags()
+    return _plane_any(_u8(v), 2, as_bool=False).reshape(-1).contiguous()
+
+
+def classification_loss(cls_out, label, unk_voxels, args, chosen_segment_mask, classes, class_weights=None):
+    """classification_loss (:614-664, the live branches) of the multi-task baseline: BCE-with-logits of the branch's outputs against "this lesion class
+    has a voxel in the label or in the chosen segment mask", weighted by `class_weights`, zero where the class has unknown voxels and no positive
+    target, mean over all B x Nc entries.  The volumes enter as presence flags only (PackedBits.class_flags() or one reduction over the planes);
+    ONE launch turns flags, logits and weights into the scalar and d logits (torch.ops.rsuper.classification_loss).  Nothing is read back."""
+    lesion_idx = [i for i, name in enumerate(classes) if 'lesion' in name]
+    B, C = label.shape[:2]
+    assert cls_out.dim() == 2 and cls_out.shape[0] == B, f'Classification output shape is: {tuple(cls_out.shape)}, label shape is: {tuple(label.shape)}'
+    if cls_out.shape[1] != len(lesion_idx):
+        raise ValueError(f'Target size ({(B, len(lesion_idx))}) must be the same as input size ({tuple(cls_out.shape)})')
+    if not cls_out.is_cuda:
+        raise _l.RSuperHipError('classification_loss needs device tensors (no CPU fallback)')
+    if C > 64 or len(classes) != C:
+        raise ValueError(f'classification_loss: {len(classes)} class names for {C} channels (at most 64)')
+    weights = None
+    if class_weights is not None:
+        weights = torch.broadcast_to(class_weights.to(cls_out.device).float(), cls_out.shape).contiguous()      # raises when it does not broadcast
+    class_set = 0
+    for i in lesion_idx:
+        class_set |= 1 << i
+    if class_set >= 1 << 63:
+        class_set -= 1 << 64                                 # the schema has no unsigned type
+    fl = _class_flags(label)
+    fm = None if chosen_segment_mask is None else _class_flags(chosen_segment_mask)
+    fu = None if unk_voxels is None else _class_flags(unk_voxels)
+    return ops.ClsLossFn.apply(cls_out, fl, fm, fu, weights, class_set)
+
+
+def clip_loss(model_output, report_embeddings, dist=None):
+    """The clip_only branch of calculate_loss (:841-856): symmetric InfoNCE between the CLIP branch's embedding and the report embedding, times the
+    world size (the reference's compensation for its gradient averaging).  `dist` None or without an initialised process group counts as one rank
+    (the reference needs an initialised torch.distributed there).  The segmentation outputs are touched with `* 0` so their parameters end the
+    backward with zero gradients -- a deep-supervision list as in the reference, and a single tensor too (where the reference fails on an
+    unassigned name)."""
+    from .info_nce import info_nce
+    seg, emb = model_output['segmentation'], model_output['clip']
+    tmp = 0
+    for s_ in (seg if isinstance(seg, (tuple, list)) else [seg]):
+        tmp = tmp + s_.sum() * 0
+    emb = emb + tmp * 0
+    assert emb.shape == report_embeddings.shape, f'Result embedding shape is: {emb.shape}, report embedding shape is: {report_embeddings.shape}'
+    world = 1
+    if dist is not None and getattr(dist, 'is_available', lambda: True)() and getattr(dist, 'is_initialized', lambda: True)():
+        world = dist.get_world_size()
+    rep = report_embeddings.to(emb.device)
+    sym = 0.5 * (info_nce(emb, rep) + info_nce(rep, emb)) * world
+    return {'contrastive_loss': sym, 'overall': sym}
+
+
 def calculate_loss(model_output, label, unk_voxels, args, matcher, chosen_segment_mask,
                    tumor_volumes_report, tumor_diameters, classes, input_tensor=None, class_weights=None,
                    model_genesis=False, clip_only=False, report_embeddings=None, dist=None, pre=None):
     """Same contract as the reference (:685-1076): returns {'segmentation', report keys..., 'overall'}."""
     if model_genesis:                                        # :838-839, before anything else
         return model_genesis_loss(model_output['segmentation'], label)
-    if clip_only or getattr(args, 'classification_branch', False) or getattr(args, 'multi_ch_tumor', False):
-        raise NotImplementedError('clip_only / classification_branch / multi_ch_tumor are baselines outside '
-                                  'the accelerated R-Super path (SURVEY.md section 2.1)')
+    if clip_only:                                            # :841-856
+        return clip_loss(model_output, report_embeddings, dist)
+    if getattr(args, 'multi_ch_tumor', False):
+        raise NotImplementedError('multi_ch_tumor is outside the accelerated R-Super path (SURVEY.md section 2.1)')
     _l.require_device()
+    cls_on = bool(getattr(args, 'classification_branch', False))       # multi-task baseline: :860-861, :885-887, :1060-1061
     merged = any(len(v) > 1 for v in lesion_channel_lists(classes).values())
     label_pk = None
     if merged:      # lesion groups spanning several channels merge whole tensors first (_calculate_loss_merged): inflate
@@ -893,6 +958,8 @@ def calculate_loss(model_output, label, unk_voxels, args, matcher, chosen_segmen
                 loss[k] = rep[k]
     else:
         loss['report'] = rep_scalar
+    if cls_on:
+        loss['classification'] = classification_loss(model_output['classification'], label, unk_voxels, args, chosen_segment_mask, classes, class_weights)
     overall = None
     for k in list(loss.keys()):
         overall = loss[k] if overall is None else overall + loss[k]
