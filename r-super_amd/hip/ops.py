@@ -214,9 +214,8 @@ _NONE = (None, 0, 0, None)
 class KernelTimer:
     """Optional HIP-event timing of the MFMA conv launches on the launch stream (used by bench.py's roofline leg).
     Records (kind, algorithmic FLOPs, start event, end event) per launch; `summary()` synchronises.
-    Weight gradients run on a side stream concurrently with the data-gradient chain, so per-launch durations overlap in
-    wall time: `busy_ms` is the length of the UNION of all launch intervals on the device timeline (time during which at
-    least one timed kernel was running) -- the denominator of an honest aggregate FLOP rate."""
+    `busy_ms` is the length of the UNION of all launch intervals on the device timeline (time during which at least one
+    timed kernel was running) -- the denominator of an honest aggregate FLOP rate."""
 
     def __init__(self, fenced=None):
         # fenced=False (default): events created with hipEventDisableSystemFence through the C ABI (rsuper_timer_event_*): a default event -- what
@@ -329,100 +328,6 @@ def grad_dest(w, shape=None):
     return torch.empty_like(w) if shape is None else torch.empty(shape, device=w.device, dtype=torch.float32)
 
 
-# ------------------------------------------------------------------------------------------------ side stream
-# Weight gradients depend only on (x, dY) and are consumed by the optimiser, so they run on a second HIP stream
-# concurrently with the data-gradient chain of the main stream (they fill CUs left idle by kernel tails and by the
-# small low-resolution layers).  The main stream joins the side stream at the end of backward (autograd callback).
-# Opt-in (RSUPER_WGRAD_OVERLAP=1): same-box 1-2 % faster steps (14.10 -> 13.99 ms), but both streams' kernels fill the
-# chip, so they mostly time-share it and every per-kernel duration (HIP events, rocprofv3) is inflated by its neighbour;
-# the default keeps one stream so kernel timings and the roofline accounting stay clean.
-_SIDE = None
-_PENDING = []
-_CALLBACK_QUEUED = False
-
-
-def overlap_mode():
-    """RSUPER_WGRAD_OVERLAP: '0' never (default), '1' always, 'auto': only where a launch cannot fill the chip.
-    Same-box step times of round 2: 12.58 ms ('0'), 12.57 ms ('auto'), 12.72 ms ('1')."""
-    return os.environ.get('RSUPER_WGRAD_OVERLAP', '0')
-
-
-def overlap_enabled(voxels=None):
-    """Weight gradients on the side stream?  `auto`: for volumes of at most 24^3 voxels per sample -- there the
-    data-gradient and the weight-gradient launches each occupy a fraction of the 256 CUs (72-144 persistent blocks), so the
-    two chains run side by side instead of taking turns; at 48^3 / 96^3 every launch fills the chip and concurrency only
-    interleaves them.  voxels=None asks whether the side stream is in use at all (the gradient reducer orders its
-    collectives after it)."""
-    m = overlap_mode()
-    if voxels is None and reduce_side_enabled():
-        return True
-    if m == '1':
-        return True
-    if m == 'auto':
-        return voxels is None or voxels <= 24 ** 3
-    return False
-
-
-def _join_per_block():
-    """Under DDP (any world size, incl. the 1-rank `bench.py --force-ddp`) the reducer's hooks copy each gradient into its
-    bucket as soon as the block's backward returns, on the main stream: the side stream is joined at the end of every
-    block's backward instead of once at the end of the whole backward pass."""
-    import torch.distributed as dist
-    # with rsuper_amd.reducer.GradReducer attached (GRAD_DEST set) the collectives are ordered on the side stream itself
-    return GRAD_DEST is None and dist.is_available() and dist.is_initialized()
-
-
-def side_stream():
-    global _SIDE
-    if _SIDE is None:
-        _SIDE = torch.cuda.Stream()
-    return _SIDE
-
-
-def join_side():
-    """Make the current (main) stream wait for all weight-gradient work queued on the side stream."""
-    global _CALLBACK_QUEUED
-    cur = torch.cuda.current_stream()
-    while _PENDING:
-        cur.wait_event(_PENDING.pop())
-    _CALLBACK_QUEUED = False
-
-
-def _queue_join():
-    global _CALLBACK_QUEUED
-    if not _CALLBACK_QUEUED:
-        _CALLBACK_QUEUED = True
-        torch.autograd.Variable._execution_engine.queue_callback(join_side)
-
-
-class _Side:
-    """Context: run the enclosed launches on the side stream after `after` (an event on the main stream)."""
-
-    def __init__(self, enabled, tensors):
-        self.enabled, self.tensors = enabled, [t for t in tensors if t is not None]
-
-    def __enter__(self):
-        if self.enabled:
-            ev = torch.cuda.Event()
-            ev.record()
-            self.ctx = torch.cuda.stream(side_stream())
-            self.ctx.__enter__()
-            side_stream().wait_event(ev)
-        return self
-
-    def __exit__(self, *a):
-        if self.enabled:
-            done = torch.cuda.Event()
-            done.record(side_stream())
-            _PENDING.append(done)
-            self.ctx.__exit__(*a)
-            for t in self.tensors:
-                t.record_stream(side_stream())     # keep inputs alive until the side stream has consumed them
-            if not _join_per_block():
-                _queue_join()
-        return False
-
-
 def igemm(epi, a, b, packed, n_cols, bn, dims, out, out_ld=None, res=None, part=None, ea=None, eb=None, out2=None, out_split=0):
     """a, b, ea, eb: Src (b/eb may be None).  res: Src or None.  dims = (N, D, H, W).
     out2 / out_split: columns [out_split, n_cols) go to the tensor `out2` (same row stride as `out`, allocated behind it in the same buffer) --
@@ -466,44 +371,28 @@ def igemm_s2(mode, a, b, packed, n_cols, full_dims, out, part, ea=None):
         run()
 
 
-def strided_kernel(dtype, dims, direction):
-    """Whether a strided [conv1 | shortcut] GEMM takes the parity-class kernel (csrc/conv3d_igemm_s2.hip: the minimal MFMA work, no
-    full-resolution temporary) or the rounds-1/2 evaluation (the tuned stride-1 kernels at full resolution + subsample / zero-stuffed dy: 8x
-    the work).  Measured on MI355X (tools/bench_conv.py, B = 2, 96^3 / 48^3 / 24^3 inputs): f32 forward 5.3x / 3.4x / 3.8x and data gradient
+def strided_kernel():
+    """Whether a strided [conv1 | shortcut] block takes the parity-class kernels (csrc/conv3d_igemm_s2.hip, csrc/conv3d_wgrad_s2.hip: the minimal
+    MFMA work, no full-resolution temporary) or the rounds-1/2 evaluation (the tuned stride-1 kernels at full resolution + subsample / zero-stuffed
+    dy: 8x the work).  Measured on MI355X (tools/bench_conv.py, B = 2, 96^3 / 48^3 / 24^3 inputs): f32 forward 5.3x / 3.4x / 3.8x and data gradient
     3.7x / 3.6x / 4.2x faster; bf16 forward 2.3x / 1.3x / 1.7x, data gradient 2.2x / 1.8x / 1.3x -- so it is the default everywhere;
     RSUPER_S2_KERNEL=0 selects the old evaluation (tests run both, A/B)."""
-    if os.environ.get('RSUPER_S2_KERNEL', '1') == '0':
-        return False
-    if direction == 'wgrad':          # csrc/conv3d_wgrad_s2.hip (round 3); RSUPER_S2_WGRAD=0: stride-1 kernel on the zero-stuffed dy
-        return os.environ.get('RSUPER_S2_WGRAD', '1') != '0'
-    return True
-
-
-def reduce_side_enabled():
-    """RSUPER_WGRAD_REDUCE_SIDE=1 (opt-in; same-box A/B 11.68 vs 11.24 ms per step: the cross-stream event waits cost more than the
-    overlap gains): the slab reduction of every weight gradient (a ~10 us bandwidth-bound kernel that only the
-    optimiser waits for) runs on the side stream, concurrently with the data-gradient chain, instead of between two of its kernels."""
-    return os.environ.get('RSUPER_WGRAD_REDUCE_SIDE', '0') == '1'
+    return os.environ.get('RSUPER_S2_KERNEL', '1') != '0'
 
 
 # Deferred slab reductions: the two weight gradients of a BasicBlock's backward (conv2; conv1 + shortcut) only write their per-split slabs, and ONE
-# batched launch at the end of the block's backward sums both -- the per-layer reduction is a ~10 us launch at the dependent-launch floor (34 per UNet
+# batched launch per block sums both -- the per-layer reduction is a ~10 us launch at the dependent-launch floor (34 per UNet
 # step).  Deferring ALL of them to the end of the backward pass was measured too (one launch of 333 us instead of 34 x 11 us: the 1.5 GB of slabs
 # are then read cold from HBM instead of hot from L2 / Infinity Cache -- no gain, and the slabs stay allocated), hence per block.
-# RSUPER_WGRAD_DEFER=0 restores the per-layer launches.
 _DEFERRED = []
-DEFER_WGRAD_REDUCE = os.environ.get('RSUPER_WGRAD_DEFER', '1') == '1'
-
-
-FUSE_STATS_REDUCE = os.environ.get('RSUPER_FUSE_STATS_REDUCE', '1') == '1'      # =0: every statistics finalisation as its own launch (A/B)
 
 
 def flush_wgrad_reduces(stats=None):
     """Sum the slabs of every weight gradient whose reduction was deferred (one launch on the current stream).  Idempotent.
     stats: up to two (part, cnt, mode, split) statistics buffers finalised by the SAME launch (rsuper_conv3_wgrad_reduce_batch_stats: the arithmetic of
-    stats_finalize, bit-identical); returns the list of their results in stats_finalize's form.  Without deferred reductions to ride on they are finalised
-    by their own launches."""
-    if stats and (not _DEFERRED or not FUSE_STATS_REDUCE or len(stats) > 2 or len(_DEFERRED) > 48):
+    stats_finalize, bit-identical); returns the list of their results in stats_finalize's form.  Without deferred reductions to ride on, or past the
+    C entry's limits (two statistics buffers, 48 gradients), they are finalised by their own launches."""
+    if stats and (not _DEFERRED or len(stats) > 2 or len(_DEFERRED) > 48):
         res = [stats_finalize(p_, cnt, mode=mode, split=split) for p_, cnt, mode, split in stats]
         flush_wgrad_reduces()
         return res
@@ -544,63 +433,31 @@ def flush_wgrad_reduces(stats=None):
     return res
 
 
-def _defer_reduce(ws, splits, Cin_t, Ya, Yb, dwa, dwb):
-    _DEFERRED.append((ws, splits, Cin_t, Ya, Yb, dwa, dwb))
-
-
-def wgrad(xa, xb, ya, yb, dwa, dwb, dims, side_reduce=False, defer=False):
-    """side_reduce (only from inside an autograd backward, where the join callback can be queued): partial slabs on the current
-    stream, their reduction into dwa / dwb on the side stream.  defer: partial slabs now, the reduction in the batched launch of the caller's
-    flush_wgrad_reduces() (before dwa / dwb leave the caller)."""
+def wgrad(xa, xb, ya, yb, dwa, dwb, dims, defer=False):
+    """Weight gradient of a 3x3x3 convolution over the sources [xa | xb] and the output gradients [ya | yb] into dwa / dwb.
+    defer: partial slabs now, the reduction in the batched launch of the caller's flush_wgrad_reduces() (before dwa / dwb leave the caller)."""
     dt = _DT[xa.t.dtype]
     N, D, H, W = dims
-    Mtot = ya.C + (yb.C if yb is not None else 0)
-    splits = _L().rsuper_conv3_wgrad_splits(dt, xa.C, xb.C if xb is not None else 0, ya.C, yb.C if yb is not None else 0, N, D, H, W)
-    assert splits >= 1
-    yb_args = (None, 0, 0) if yb is None else (_ptr(yb.t, yb.off), yb.ld, yb.C)
+    Ya, Yb = ya.C, yb.C if yb is not None else 0
     Cin_t = xa.C + (xb.C if xb is not None else 0)
-    ws = torch.empty((splits * 27 * Mtot * Cin_t,), device=dwa.device, dtype=torch.float32)
-    flops = 2.0 * N * D * H * W * Mtot * Cin_t * 27
+    splits = _L().rsuper_conv3_wgrad_splits(dt, xa.C, Cin_t - xa.C, Ya, Yb, N, D, H, W)
+    assert splits >= 1
+    ws = torch.empty((splits * 27 * (Ya + Yb) * Cin_t,), device=dwa.device, dtype=torch.float32)
+    operands = (dt, use_tr(), *xa.args(), *(xb.args() if xb is not None else _NONE),
+                _ptr(ya.t, ya.off), ya.ld, Ya, *((None, 0, 0) if yb is None else (_ptr(yb.t, yb.off), yb.ld, Yb)))
+    tail = (_ptr(ws), N, D, H, W, splits, _stream())
 
-    if defer and not side_reduce:
-        def run_partial_only():
-            _l.check(_L().rsuper_conv3_wgrad_partial(dt, use_tr(), *xa.args(), *(xb.args() if xb is not None else _NONE),
-                                                     _ptr(ya.t, ya.off), ya.ld, ya.C, *yb_args, _ptr(ws), N, D, H, W, splits, _stream()),
-                     'conv3_wgrad_partial')
-        if TIMER is not None:
-            TIMER.launch('conv3d_wgrad', flops, run_partial_only)
+    def run():
+        if defer:
+            _l.check(_L().rsuper_conv3_wgrad_partial(*operands, *tail), 'conv3_wgrad_partial')
         else:
-            run_partial_only()
-        _defer_reduce(ws, splits, Cin_t, ya.C, yb.C if yb is not None else 0, dwa, dwb)
-        return
-    if not side_reduce:
-        def run():
-            _l.check(_L().rsuper_conv3_wgrad(dt, use_tr(), *xa.args(), *(xb.args() if xb is not None else _NONE),
-                                             _ptr(ya.t, ya.off), ya.ld, ya.C, *yb_args, _ptr(dwa), _ptr(dwb), _ptr(ws), N, D, H, W, splits,
-                                             _stream()), 'conv3_wgrad')
-        if TIMER is not None:
-            TIMER.launch('conv3d_wgrad', flops, run)
-        else:
-            run()
-        return
-
-    def run_partial():
-        _l.check(_L().rsuper_conv3_wgrad_partial(dt, use_tr(), *xa.args(), *(xb.args() if xb is not None else _NONE),
-                                                 _ptr(ya.t, ya.off), ya.ld, ya.C, *yb_args, _ptr(ws), N, D, H, W, splits, _stream()),
-                 'conv3_wgrad_partial')
-
-    def run_reduce():
-        _l.check(_L().rsuper_conv3_wgrad_reduce(_ptr(ws), splits, Cin_t, ya.C, yb.C if yb is not None else 0, _ptr(dwa), _ptr(dwb),
-                                                _stream()), 'conv3_wgrad_reduce')
+            _l.check(_L().rsuper_conv3_wgrad(*operands, _ptr(dwa), _ptr(dwb), *tail), 'conv3_wgrad')
     if TIMER is not None:
-        TIMER.launch('conv3d_wgrad', flops, run_partial)
+        TIMER.launch('conv3d_wgrad', 2.0 * N * D * H * W * (Ya + Yb) * Cin_t * 27, run)
     else:
-        run_partial()
-    with _Side(True, (ws, dwa, dwb)):
-        if TIMER is not None:
-            TIMER.launch('conv3d_wgrad_reduce', 0.0, run_reduce)      # events on the side stream: counted in the union of intervals
-        else:
-            run_reduce()
+        run()
+    if defer:
+        _DEFERRED.append((ws, splits, Cin_t, Ya, Yb, dwa, dwb))
 
 
 def wgrad_s2(xa, ya, yb, dwa, dwb, full_dims):
@@ -642,10 +499,10 @@ class BasicBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xa, mra, xb, mrb, w1, w2, ws, packs=None, stride=1):
-        """packs: optional (tensors, bns) from pack_weights_batch / block_pack_specs (whole-network batched packing).
+        """packs: optional (tensors, bns) from block_packs (the module's no-grad cache of forward fragments).
         stride 2 (down_block(pool=False), unet_utils.py:38-39): conv1 and the shortcut conv run as one strided GEMM on the parity-class
-        kernel (csrc/conv3d_igemm_s2.hip: the minimal MFMA work, forward and data gradient; their weight gradient still reads a
-        zero-stuffed dy at full resolution), conv2 at the half resolution."""
+        kernels (csrc/conv3d_igemm_s2.hip forward and data gradient, csrc/conv3d_wgrad_s2.hip weight gradient: the minimal MFMA work,
+        no zero-stuffed dy), conv2 at the half resolution."""
         if stride == 2:
             return _BB._forward_s2(ctx, xa, mra, w1, w2, ws)
         assert stride == 1
@@ -674,8 +531,7 @@ class BasicBlockFn(torch.autograd.Function):
         # [y1 | shortcut] halves narrower than a 128-byte line (32 bf16 channels: up4.0): two tensors instead of an interleaved one, so that conv2's staging,
         # its weight gradient, the mask of its data gradient and the InstanceNorm-backward tail read whole cache lines (rsuper_conv3_igemm_split_out; the
         # depth-reuse kernel's epilogue only -- other kernels keep the interleaved output)
-        split_ys = (has_sc and Cout * xa.element_size() < 128 and Cout % 32 == 0 and os.environ.get('RSUPER_SPLIT_YS', '1') == '1'
-                    and igemm_plan(dt, 0, dims, nc1, bn1, mixed)[0] == _l.IGEMM_KD)
+        split_ys = has_sc and Cout * xa.element_size() < 128 and Cout % 32 == 0 and igemm_plan(dt, 0, dims, nc1, bn1, mixed)[0] == _l.IGEMM_KD
         if split_ys:
             ys2 = torch.empty((2, N, D, H, W, Cout), device=dev, dtype=dt)
             ys, sc_t = ys2[0], ys2[1]
@@ -708,7 +564,7 @@ class BasicBlockFn(torch.autograd.Function):
         tiles = _L().rsuper_conv3_tiles(D, H, W)
         sa = Src(xa, mr=mra)
         nc1 = 2 * Cout
-        if not strided_kernel(dt, dims, 'fwd'):
+        if not strided_kernel():
             specs, bns = block_pack_specs(w1, w2, ws, Ca, 0, dt, tiles * N, False, dims)
             wp = pack_weights_batch(dt, specs)
             full = torch.empty((N, D, H, W, nc1), device=dev, dtype=dt)
@@ -767,27 +623,24 @@ class BasicBlockFn(torch.autograd.Function):
         sa = Src(xa, mr=mra)
         tiles = _L().rsuper_conv3_tiles(D, H, W)
         g0 = torch.empty((N, D, H, W, Ca), device=dev, dtype=dt)
-        k_dgrad, k_wgrad = strided_kernel(dt, dims, 'dgrad'), strided_kernel(dt, dims, 'wgrad')
-        dfull = None
-        if not (k_dgrad and k_wgrad):
-            dfull = torch.empty((N, D, H, W, 2 * Cout), device=dev, dtype=dt)
-            subsample2_scatter(dy1, dfull, 0, dims)
-            subsample2_scatter(dout, dfull, Cout, dims)
-        if not k_dgrad:
-            bnd = pick_bn(Ca, dt, tiles * N, dims, epi=1)
-            wpd1 = pack_weights(dt, 1, w1, ws, Cout, Cout, Ca, 0, bnd)
-            part0 = part_buffer(dt, dims, Ca, bnd, dev, epi=1)
-            igemm(1, Src(dfull, C=Cout), Src(dfull, C=Cout, off=Cout), wpd1, Ca, bnd, dims, g0, part=part0, ea=sa)
-        else:
+        if strided_kernel():
             # the transposed convolution by output parity classes, straight from [dy1 | dOut] on the half grid (no zero-stuffed operand)
             wpd1 = pack_weights(dt, 1, w1, ws, Cout, Cout, Ca, 0, 64)
             part0 = torch.empty((N, _L().rsuper_conv3_s2_part_rows(_DT[dt], 2, Cout, Cout, Ca, N, D, H, W), Ca, 2), device=dev, dtype=torch.float32)
             igemm_s2(2, Src(dy1), sdo, wpd1, Ca, dims, g0, part0, ea=sa)
-        gm0 = stats_finalize(part0, D * H * W, mode=1)
-        dw1, dws = grad_dest(w1), grad_dest(ws)
-        if k_wgrad:
+            gm0 = stats_finalize(part0, D * H * W, mode=1)
+            dw1, dws = grad_dest(w1), grad_dest(ws)
             wgrad_s2(sa, Src(dy1), sdo, dw1, dws, dims)
         else:
+            dfull = torch.empty((N, D, H, W, 2 * Cout), device=dev, dtype=dt)
+            subsample2_scatter(dy1, dfull, 0, dims)
+            subsample2_scatter(dout, dfull, Cout, dims)
+            bnd = pick_bn(Ca, dt, tiles * N, dims, epi=1)
+            wpd1 = pack_weights(dt, 1, w1, ws, Cout, Cout, Ca, 0, bnd)
+            part0 = part_buffer(dt, dims, Ca, bnd, dev, epi=1)
+            igemm(1, Src(dfull, C=Cout), Src(dfull, C=Cout, off=Cout), wpd1, Ca, bnd, dims, g0, part=part0, ea=sa)
+            gm0 = stats_finalize(part0, D * H * W, mode=1)
+            dw1, dws = grad_dest(w1), grad_dest(ws)
             wgrad(sa, None, Src(dfull, C=Cout), Src(dfull, C=Cout, off=Cout), dw1, dws, dims)
         dxa = in_bwd_finalize(Src(g0), sa, gm0, Ca)
         return dxa, None, None, None, dw1, dw2, dws, None, None
@@ -829,66 +682,40 @@ class BasicBlockFn(torch.autograd.Function):
         part = part_buffer(dt, dims, Cout, bn, dev, epi=1)
         igemm(1, sdo, None, wpd2, Cout, bn, dims, g1, part=part, ea=y1)
         gm1 = stats_finalize(part, cnt, mode=1)
-        # the join with the side stream is deferred to the end of backward: only safe when AccumulateGrad merely stores
-        # the new gradient (p.grad is None, zero_grad(set_to_none=True)); an in-place `p.grad += dw` would race
-        fresh = all(w.grad is None for w in (w1, w2, ws) if w is not None)
-        ov = overlap_enabled(D * H * W) and fresh
-        sr = reduce_side_enabled() and fresh and not ov
         dw2 = grad_dest(w2)
-        with _Side(ov, (ys, mr_y1, dout, dw2)):
-            wgrad(y1, None, sdo, None, dw2, None, dims, side_reduce=sr, defer=DEFER_WGRAD_REDUCE and not ov)
+        wgrad(y1, None, sdo, None, dw2, None, dims, defer=True)
         dy1 = in_bwd_finalize(Src(g1), y1, gm1, Cout)
         # conv1 (+ shortcut): fused data gradient over [dY1 | dOut], fused weight gradient
         sa = Src(xa, mr=mra)
         sb = None if xb is None else Src(xb, mr=mrb)
-        # one gradient tensor per forward source when each source has its own launch (a 32-channel slice of a 96-channel row is 64 of every 192 bytes: the
-        # InstanceNorm-backward tails then fetch half-used cache lines -- up4.0: 80 / 145 us for the two tails against 61 / 123 us on contiguous tensors)
-        split_g0 = len(bpk[0]) == 3 and os.environ.get('RSUPER_SPLIT_G0', '1') == '1'
-        g0 = None if split_g0 else torch.empty((N, D, H, W, Cin), device=dev, dtype=dt)
-        g0s = [torch.empty((N, D, H, W, Ca), device=dev, dtype=dt), torch.empty((N, D, H, W, Cb), device=dev, dtype=dt)] if split_g0 else None
-        # With the slab reductions deferred to one launch per block, that launch also finalises the InstanceNorm-backward rows of this data gradient
-        # (flush_wgrad_reduces(stats=...)): it then runs BEFORE the InstanceNorm-backward tail instead of after it.
-        fuse = FUSE_STATS_REDUCE and DEFER_WGRAD_REDUCE and not ov and not sr
-        pending = []
+        sdo1 = sdo if has_sc else None
         if len(bpk[0]) == 3:                  # one launch per forward source (block_pack_specs / split_dgrad_sources)
-            gm0 = []
-            for si, (c0, cn, src, wp_, bn) in enumerate(((0, Ca, sa, bpk[0][1], bpk[1][1]), (Ca, Cb, sb, bpk[0][2], bpk[1][2]))):
-                part0 = part_buffer(dt, dims, cn, bn, dev, epi=1)
-                if split_g0:
-                    igemm(1, Src(dy1), sdo if has_sc else None, wp_, cn, bn, dims, g0s[si], part=part0, ea=src)
-                else:
-                    igemm(1, Src(dy1), sdo if has_sc else None, wp_, cn, bn, dims, g0[..., c0:], out_ld=Cin, part=part0, ea=src)
-                if fuse:
-                    pending.append((part0, cnt, 1, 0))
-                else:
-                    gm0.append(stats_finalize(part0, cnt, mode=1))
+            # and one gradient tensor per source (a 32-channel slice of a 96-channel row is 64 of every 192 bytes: the InstanceNorm-backward tails
+            # then fetch half-used cache lines -- up4.0: 80 / 145 us for the two tails against 61 / 123 us on contiguous tensors)
+            g0s = [Src(torch.empty((N, D, H, W, Ca), device=dev, dtype=dt)), Src(torch.empty((N, D, H, W, Cb), device=dev, dtype=dt))]
+            stats = []
+            for g, src, wp_, bn in ((g0s[0], sa, bpk[0][1], bpk[1][1]), (g0s[1], sb, bpk[0][2], bpk[1][2])):
+                part0 = part_buffer(dt, dims, src.C, bn, dev, epi=1)
+                igemm(1, Src(dy1), sdo1, wp_, src.C, bn, dims, g.t, part=part0, ea=src)
+                stats.append((part0, cnt, 1, 0))
         else:
+            g0 = torch.empty((N, D, H, W, Cin), device=dev, dtype=dt)
+            g0s = [Src(g0, C=Ca), Src(g0, C=Cb, off=Ca)]
             bn, wpd1 = bpk[1][1], bpk[0][1]
             part0 = part_buffer(dt, dims, Cin, bn, dev, epi=1)
-            igemm(1, Src(dy1), sdo if has_sc else None, wpd1, Cin, bn, dims, g0, part=part0, ea=sa, eb=sb)
-            if fuse:
-                pending.append((part0, cnt, 1, 0 if xb is None else Ca))
-            else:
-                gm0 = stats_finalize(part0, cnt, mode=1, split=0 if xb is None else Ca)
+            igemm(1, Src(dy1), sdo1, wpd1, Cin, bn, dims, g0, part=part0, ea=sa, eb=sb)
+            stats = [(part0, cnt, 1, Ca if xb is not None else 0)]
         dw1 = grad_dest(w1)
         dws = grad_dest(ws) if has_sc else None
-        with _Side(ov, (xa, mra, xb, mrb, dy1, dout, dw1, dws)):
-            wgrad(sa, sb, Src(dy1), sdo if has_sc else None, dw1, dws, dims, side_reduce=sr, defer=DEFER_WGRAD_REDUCE and not ov)
-        if fuse:
-            fin = flush_wgrad_reduces(stats=pending)
-            gm0 = fin if len(bpk[0]) == 3 else fin[0]
+        wgrad(sa, sb, Src(dy1), sdo1, dw1, dws, dims, defer=True)
+        # both weight gradients of the block: one reduction launch, slabs still hot in L2.  It also finalises the InstanceNorm-backward rows of this
+        # data gradient, so it runs BEFORE the InstanceNorm-backward tails.
+        gm0 = flush_wgrad_reduces(stats=stats)
         if xb is None:
-            dxa = in_bwd_finalize(Src(g0), sa, gm0, Ca, add1=None if has_sc else dout)
-            dxb = None
-        elif split_g0:
-            dxa = in_bwd_finalize(Src(g0s[0]), sa, gm0[0], Ca)
-            dxb = in_bwd_finalize(Src(g0s[1]), sb, gm0[1], Cb)
+            dxa, dxb = in_bwd_finalize(g0s[0], sa, gm0[0], Ca, add1=None if has_sc else dout), None
         else:
-            dxa = in_bwd_finalize(Src(g0, C=Ca), sa, gm0[0], Ca)
-            dxb = in_bwd_finalize(Src(g0, C=Cb, off=Ca), sb, gm0[1], Cb)
-        flush_wgrad_reduces()                 # both weight gradients of the block: one reduction launch, slabs still hot in L2
-        if (ov or sr) and _join_per_block():
-            join_side()
+            gma, gmb = gm0 if len(gm0) == 2 else gm0[0]       # one table per launch, or the joint launch's table split at Ca
+            dxa, dxb = in_bwd_finalize(g0s[0], sa, gma, Ca), in_bwd_finalize(g0s[1], sb, gmb, Cb)
         return dxa, None, dxb, None, dw1, dw2, dws, None, None
 
 

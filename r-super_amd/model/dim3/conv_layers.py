@@ -43,8 +43,8 @@ class BasicBlock(nn.Module):
 
     def forward(self, xa, mra, xb=None, mrb=None):
         w1, w2, ws = self.weights()
-        packs = getattr(self, '_packs', None)        # set by UNet.forward (whole-network batched weight packing)
-        if packs is None and not torch.is_grad_enabled():
+        packs = None
+        if not torch.is_grad_enabled():
             packs = self._cached_forward_packs(xa, xb, w1, w2, ws, xb is not None and (mra is None) != (mrb is None))
         if self.stride == 2:
             assert xb is None

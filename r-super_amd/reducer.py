@@ -4,10 +4,9 @@ Same mathematics as torch DDP (every rank ends the backward pass with the mean o
 broadcast from rank 0 at construction), laid out for this step:
   * gradients live in a few flat f32 buckets (reverse registration order ~ the order backward produces them); the HIP
     weight-gradient kernels write straight into bucket views (`ops.grad_dest`), so there is no per-parameter copy;
-  * a post-accumulate hook only counts; when a bucket is complete ONE asynchronous all-reduce is issued -- on RCCL from
-    the weight-gradient side stream, so the collective is ordered after the kernels that filled the bucket and overlaps
-    the data-gradient chain on the main stream (torch DDP's per-parameter hooks on the main stream rule that overlap out
-    and cost ~1 ms of host/stream bookkeeping per step here);
+  * a post-accumulate hook only counts; when a bucket is complete ONE asynchronous all-reduce is issued from the
+    stream of backward, so the collective is ordered after the kernels that filled the bucket (torch DDP's per-parameter
+    hooks cost ~1 ms of host/stream bookkeeping per step here);
   * `finish()` (after backward, before clip/optimiser) makes the main stream wait for the collectives.
 RCCL averages in the collective (ReduceOp.AVG); gloo (CPU tests) sums and divides.
 """
@@ -115,16 +114,6 @@ class GradReducer:
 
     def _launch(self, b):
         op = dist.ReduceOp.AVG if self.backend == 'nccl' else dist.ReduceOp.SUM
-        if b.flat.is_cuda:
-            from .hip import ops
-            side = ops.side_stream() if ops.overlap_enabled() else None
-            if side is not None:
-                ev = torch.cuda.Event()
-                ev.record()                                     # gradients produced on the main stream (stem, head, copies)
-                with torch.cuda.stream(side):
-                    side.wait_event(ev)
-                    b.handle = dist.all_reduce(self._wire(b), op=op, group=self.pg, async_op=True)
-                return
         b.handle = dist.all_reduce(self._wire(b), op=op, group=self.pg, async_op=True)
 
     def finish(self):
@@ -136,8 +125,8 @@ class GradReducer:
             b.handle = None
             if self.wire_dtype is not None:
                 b.flat.copy_(b.wire)                            # back into the f32 bucket the optimiser reads (after the wait: stream-ordered)
-                if b.wire.is_cuda:                              # allocated on the side stream, read here on the current one: the caching
-                    b.wire.record_stream(torch.cuda.current_stream())   # allocator must not recycle it for a side-stream tensor before this copy ran
+                if b.wire.is_cuda:                              # allocated on the stream the gradient hook ran on, read here on the current one:
+                    b.wire.record_stream(torch.cuda.current_stream())   # should they differ, the caching allocator must not recycle it before this copy ran
                 b.wire = None
             if self.backend != 'nccl':
                 b.flat.div_(self.world)

@@ -279,28 +279,8 @@ def _topk_mask(x, ball, k):
     out = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
     if k <= 0:
         return out.zero_()
-    if os.environ.get('RSUPER_TOPK_HOST', '0') != '1':
-        # device-resident radix select: one C call, no device->host reads
-        ws = torch.empty(260, device=x.device, dtype=torch.int32)
-        _l.check(_L().rsuper_topk_select(_ptr(x), _ptr(ball), V, k, _ptr(out), _ptr(ws), _stream()), 'topk_select')
-        return out
-    prefix, remaining, ties = 0, k, 0
-    hist = torch.empty(256, device=x.device, dtype=torch.int32)
-    for shift in (24, 16, 8, 0):
-        hist.zero_()
-        _l.check(_L().rsuper_radix_hist(_ptr(x), _ptr(ball), V, prefix, shift, _ptr(hist), _stream()), 'radix_hist')
-        h = hist.cpu().numpy().astype(np.int64)
-        acc = 0
-        for digit in range(255, -1, -1):       # largest values first
-            if acc + h[digit] >= remaining:
-                prefix |= digit << shift
-                remaining -= acc
-                ties = int(h[digit])          # after the last pass: number of elements equal to the threshold
-                break
-            acc += h[digit]
-    # `prefix` = bit pattern of the k-th largest value; `remaining` = how many elements equal to it are still needed
-    need = 0xFFFFFFFF if remaining >= ties else remaining      # all ties wanted -> order-free parallel marking
-    _l.check(_L().rsuper_topk_mark(_ptr(x), _ptr(ball), V, prefix, need, _ptr(out), _stream()), 'topk_mark')
+    ws = torch.empty(260, device=x.device, dtype=torch.int32)          # device-resident radix select: one C call, no device->host reads
+    _l.check(_L().rsuper_topk_select(_ptr(x), _ptr(ball), V, k, _ptr(out), _ptr(ws), _stream()), 'topk_select')
     return out
 
 
@@ -345,7 +325,7 @@ def isolate_tumor(x, diameter, gaussian, gaussian_std, tumor_volume, diameter_ma
         if new_dim >= max(D, H, W):
             break
         ball, bsum = _insert_ball((D, H, W), center, new_dim, diameter_margin, x.device)
-    if min(ks) > 0 and os.environ.get('RSUPER_TOPK_HOST', '0') != '1':
+    if min(ks) > 0:
         # the three selections share x and the ball: one batched radix select, AND with the ball folded into the marking (:1504-1507)
         import ctypes
         out3 = torch.empty((3,) + tuple(x.shape), device=x.device, dtype=torch.uint8)
@@ -380,7 +360,7 @@ def isolate_tumor_spec(x, diameter, gaussian_std, tumor_volume, checks, diameter
     D, H, W = x.shape
     V = x.numel()
     diameter, vol, ks = _isolate_params(diameter, tumor_volume, V, volume_margin)
-    if min(ks) <= 0 or os.environ.get('RSUPER_TOPK_HOST', '0') == '1':
+    if min(ks) <= 0:
         return None
     import ctypes
     best = ops.ball_search(x, diameter, float(gaussian_std * (diameter / 2.0)))

@@ -1626,3 +1626,74 @@ def test_wgrad_entry_points_agree_on_every_kernel_of_the_plan(S, Ca, Ya, thr, sp
     e = gc.relerr(dws[1], ref)
     print(f'wgrad plan {tuple(plan)} S{S} {Ca}->{Ya}: dW vs float64 {e:.2e} (bound 1e-4)')
     assert e <= 1e-4, e
+
+
+def _bits(t):
+    """Bit patterns on the host: a non-finite value cannot hide a difference (NaN != NaN) or fake one."""
+    if isinstance(t, (tuple, list)):
+        return [_bits(v) for v in t]
+    return t.contiguous().view(torch.int32).cpu()
+
+
+def _same_bits(got, ref):
+    got, ref = _bits(got), _bits(ref)
+    if isinstance(ref, list):
+        return len(got) == len(ref) and all(_same_bits(g, r) for g, r in zip(got, ref))
+    return got.shape == ref.shape and torch.equal(got, ref)
+
+
+def test_deferred_wgrad_reduction_and_fused_statistics_match_their_own_launches(monkeypatch):
+    """The step's only slab reduction, rsuper_conv3_wgrad_reduce_batch / _batch_stats behind ops.flush_wgrad_reduces, against the launches it replaces:
+    wgrad(defer=True) + one flush gives the bits of the immediate wgrad (a single-source and a two-source gradient in the same flush), the statistics
+    that ride on the flush give the bits of stats_finalize (plain and split form, InstanceNorm-backward sums and forward mean / rstd), and past the C
+    entry's limits (nothing deferred, more than two statistics buffers) stats_finalize itself runs and the deferred gradients are still reduced.
+    N = 2, 8x8x16 (4 tiles per sample), bf16, 32 channels per source and per output; every destination starts as NaN."""
+    from rsuper_amd.hip import ops
+    N, S, C = 2, (8, 8, 16), 32
+    dims, cnt = (N,) + S, S[0] * S[1] * S[2]
+    xa, xb, ya, yb = (ops.Src(gc.to_cl(gc._rng_t(seed, (N, C) + S), torch.bfloat16)) for seed in (31, 32, 33, 34))
+    parts = [gc._rng_t(seed, (N, 4, 2 * C, 2)).to(DEV) for seed in (41, 42, 43)]
+    nan = lambda *shape: torch.full(shape, float('nan'), device=DEV)          # noqa: E731
+    finalize, calls = ops.stats_finalize, []
+    monkeypatch.setattr(ops, 'stats_finalize', lambda *a, **k: (calls.append(1), finalize(*a, **k))[1])
+
+    def both(defer):
+        dw = [nan(C, C, 3, 3, 3), nan(C, 2 * C, 3, 3, 3), nan(C, 2 * C, 3, 3, 3)]
+        ops.wgrad(xa, None, ya, None, dw[0], None, dims, defer=defer)
+        ops.wgrad(xa, xb, ya, yb, dw[1], dw[2], dims, defer=defer)
+        assert len(ops._DEFERRED) == (2 if defer else 0)
+        if defer:
+            assert all(bool(torch.isnan(d).all()) for d in dw)                # the partial launches leave dW alone
+        return dw
+
+    assert not ops._DEFERRED
+    try:
+        ref_dw = both(False)
+        assert all(bool(torch.isfinite(d).all()) for d in ref_dw)
+        # deferred against immediate
+        dw = both(True)
+        assert ops.flush_wgrad_reduces() is None and not ops._DEFERRED
+        assert _same_bits(dw, ref_dw)
+        # statistics finalised by the reduction launch against stats_finalize
+        for mode in (1, 0):
+            stats = [(parts[0], cnt, mode, 0), (parts[1], cnt, mode, C)]
+            ref_st = [finalize(p, c, mode=m, split=s) for p, c, m, s in stats]
+            assert isinstance(ref_st[1], tuple) and [tuple(t.shape) for t in ref_st[1]] == [(N, C, 2)] * 2
+            dw = both(True)
+            got = ops.flush_wgrad_reduces(stats=stats)
+            assert not calls and not ops._DEFERRED
+            assert _same_bits(got, ref_st), mode
+            assert _same_bits(dw, ref_dw), mode
+        # fallbacks: nothing to ride on; more statistics buffers than the C entry takes
+        got = ops.flush_wgrad_reduces(stats=stats)
+        assert len(calls) == 2 and _same_bits(got, ref_st)
+        del calls[:]
+        stats = stats + [(parts[2], cnt, 1, 0)]
+        ref_st = ref_st + [finalize(parts[2], cnt, mode=1)]
+        dw = both(True)
+        got = ops.flush_wgrad_reduces(stats=stats)
+        assert len(calls) == 3 and not ops._DEFERRED
+        assert _same_bits(got, ref_st)
+        assert _same_bits(dw, ref_dw)
+    finally:
+        del ops._DEFERRED[:]
