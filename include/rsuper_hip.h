@@ -525,6 +525,14 @@ int rsuper_count(const uint8_t* m, long V, unsigned int* count, void* stream);
 long rsuper_detection_workspace_bytes(int planes);
 int rsuper_detection(const float* x, int planes, int Di, int Hi, int Wi, int Do, int Ho, int Wo, const double* thresholds, int nthr, int erode,
                      long long* volumes, double* max_prob, void* workspace, void* stream);
+/* test_with_reports.detection :56-94 for `planes` volumes x[planes][Di][Hi][Wi] (u8 bytes when is_u8, else f32): m = value > th (in f64, like
+ * get_fdata(); a value equal to th is not set), ndimage.zoom(m, order=0) onto [Do][Ho][Wo] -- source index floor(c + 0.5) per axis with
+ * c = o * (n_in - 1) / (n_out - 1) in f64 (0 for n_out == 1), and the constant 0 where c > n_in - 1 (scipy's 'constant' mode, as for order 1 above)
+ * -- then, with erode, binary_dilation(binary_erosion(z, box3), box3, iterations=2) & z, else z; counts: device [planes] i64 = the set voxels.
+ * Same tile, LDS passes and integer bins as rsuper_detection; workspace: rsuper_detection_workspace_bytes(planes) bytes on the device.
+ * Null pointers, planes outside 1..65535, a NaN th or an empty / over-large grid -> RSUPER_ERR_ARG, checked before anything is launched. */
+int rsuper_detection_binary(const void* x, int is_u8, int planes, int Di, int Hi, int Wi, int Do, int Ho, int Wo, double th, int erode,
+                            long long* counts, void* workspace, void* stream);
 /* postprocess_npz :655-688 (--organ_mask_on_lesion) on pred[C][D][H][W]: out[k] = pred[lesion[k]] * binary_dilation(organ > 0.5, box3), organ =
  * pred[organ_a[k]] (+ pred[organ_b[k]] when organ_b[k] >= 0).  u8: labels, the sum wraps as uint8; f32: probabilities, the sum is an f32 add.
  * lesion / organ_a / organ_b: HOST arrays of n plane indices; out: device [n][D][H][W]. */

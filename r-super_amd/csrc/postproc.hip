@@ -1,6 +1,8 @@
 // Post-processing of the predicted volumes (predict_abdomenatlas.py / eval_AUC.py; integer and byte kernels, no MFMA):
 //   detection      eval_AUC.detection :56-112: f64 align-corners trilinear zoom + 9-threshold erode / dilate / AND chain, collapsed to one
 //                  integer pass over the output grid: L = #thresholds exceeded, F = min(max5(min3(L)), L), volume(t) = #(F > t)
+//   binary det.    test_with_reports.detection :56-94: `value > th`, order-0 zoom, erode / dilate x 2 / AND, count: the one-threshold case of the
+//                  tile pass above with a nearest sample; uint8 planes read as bytes
 //   organ mask     postprocess_npz :655-688: lesion * box3_dilate(organ_a (+ organ_b) > 0.5)
 //   largest cc     keep_largest_component :692-716: 6-connected union-find, root = smallest linear index, largest size / first root
 // Every cross-workgroup result is an integer atomic (histogram bins, u64 max keys, union-find links): deterministic by construction.
@@ -170,6 +172,69 @@ __global__ __launch_bounds__(NT) void detect_finalize_kernel(const unsigned long
         volumes[(long)p * nth + t] = (long long)s;
     }
     if (threadIdx.x == 0) max_prob[p] = key_f64(row[DT_BINS]);
+}
+
+// ------------------------------------------------------------------------------------------------ binary detection
+// test_with_reports.detection :56-94: the one-threshold case of detect_kernel on a mask binarised BEFORE the zoom, sampled with ndimage.zoom's
+// order 0.  Source index of output o along an axis: floor(c + 0.5) with c = o * s; -1 (the constant 0) beyond the last input sample, as in zoom_axis.
+__device__ __forceinline__ int nearest_axis(int o, double s, int n) {
+    const double c = (double)o * s;
+    if (c > (double)(n - 1)) return -1;
+    return (int)(c + 0.5);                               // 0 <= c <= n - 1: truncation == floor, and the index stays <= n - 1
+}
+
+// Same tile, halo and LDS box_pass chain as detect_kernel with levels in {0, 1}; T = uint8_t (labels, bool) or float, `value > th` in f64 like
+// get_fdata().  The set voxels of the tile go to bin 1 of the plane's workspace row, one integer atomic per block.
+template <typename T, bool ERODE>
+__global__ __launch_bounds__(NT) void detect_binary_kernel(const T* __restrict__ x, long in_plane, ZoomGrid g, double th, int tiles_x, int tiles_y,
+                                                           unsigned long long* __restrict__ ws) {
+    constexpr int HL = ERODE ? 3 : 0;
+    constexpr int RZ = DT_Z + 2 * HL, RY = DT_Y + 2 * HL, RX = DT_X + 2 * HL;
+    constexpr int NA = ERODE ? RZ * RY * (RX - 2) : 1, NB = ERODE ? RZ * (RY - 2) * (RX - 2) : 1;
+    __shared__ uint8_t r0[RZ * RY * RX];
+    __shared__ uint8_t ba[NA], bb[NB];
+    __shared__ unsigned int cnt;
+    const int p = blockIdx.y;
+    const T* xp = x + (long)p * in_plane;
+    const int tile = blockIdx.x, tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, tz = tile / tiles_x / tiles_y;
+    const int oz = tz * DT_Z - HL, oy = ty * DT_Y - HL, ox = tx * DT_X - HL;
+    if (threadIdx.x == 0) cnt = 0u;
+    for (int i = threadIdx.x; i < RZ * RY * RX; i += NT) {
+        const int rx = i % RX, t = i / RX, ry = t % RY, rz = t / RY;
+        const int gz = oz + rz, gy = oy + ry, gx = ox + rx;
+        uint8_t l = 0;                                   // outside the volume: 0 (erosion's border_value = 0)
+        if (gz >= 0 && gz < g.Do && gy >= 0 && gy < g.Ho && gx >= 0 && gx < g.Wo) {
+            const int iz = nearest_axis(gz, g.sz, g.Di), iy = nearest_axis(gy, g.sy, g.Hi), ix = nearest_axis(gx, g.sx, g.Wi);
+            if (iz >= 0 && iy >= 0 && ix >= 0) l = (double)xp[((long)iz * g.Hi + iy) * g.Wi + ix] > th ? 1 : 0;
+        }
+        r0[i] = l;
+    }
+    __syncthreads();
+    const uint8_t* fin = r0;
+    if constexpr (ERODE) {
+        box_pass<false, 3, 0>(r0, ba, RZ, RY, RX);
+        box_pass<false, 3, 1>(ba, bb, RZ, RY, RX - 2);
+        box_pass<false, 3, 2>(bb, ba, RZ, RY - 2, RX - 2);
+        box_pass<true, 5, 0>(ba, bb, RZ - 2, RY - 2, RX - 2);
+        box_pass<true, 5, 1>(bb, ba, RZ - 2, RY - 2, DT_X);
+        box_pass<true, 5, 2>(ba, bb, RZ - 2, DT_Y, DT_X);
+        fin = bb;
+    }
+    unsigned int n = 0u;
+    for (int i = threadIdx.x; i < DT_Z * DT_Y * DT_X; i += NT) {
+        const int lx = i % DT_X, t = i / DT_X, ly = t % DT_Y, lz = t / DT_Y;
+        if (oz + HL + lz >= g.Do || oy + HL + ly >= g.Ho || ox + HL + lx >= g.Wo) continue;
+        uint8_t f = r0[((lz + HL) * RY + ly + HL) * RX + lx + HL];
+        if constexpr (ERODE) f = fin[i] < f ? fin[i] : f;
+        n += f;
+    }
+    if (n) atomicAdd(&cnt, n);
+    __syncthreads();
+    if (threadIdx.x == 0 && cnt) atomicAdd(&ws[(long)p * (DT_BINS + 1) + 1], (unsigned long long)cnt);
+}
+
+__global__ __launch_bounds__(NT) void detect_binary_finalize_kernel(const unsigned long long* __restrict__ ws, int planes, long long* counts) {
+    for (int p = blockIdx.x * NT + threadIdx.x; p < planes; p += gridDim.x * NT) counts[p] = (long long)ws[(long)p * (DT_BINS + 1) + 1];
 }
 
 // ------------------------------------------------------------------------------------------------ organ mask
@@ -347,6 +412,36 @@ int rsuper_detection(const float* x, int planes, int Di, int Hi, int Wi, int Do,
     if (erode) hipLaunchKernelGGL(detect_kernel<true>, grid, dim3(NT), 0, st, x, in_plane, g, th, nthr, tx, ty, ws);
     else hipLaunchKernelGGL(detect_kernel<false>, grid, dim3(NT), 0, st, x, in_plane, g, th, nthr, tx, ty, ws);
     hipLaunchKernelGGL(detect_finalize_kernel, dim3(planes), dim3(NT), 0, st, (const unsigned long long*)ws, nthr, volumes, max_prob);
+    return rs_check_launch();
+}
+
+int rsuper_detection_binary(const void* x, int is_u8, int planes, int Di, int Hi, int Wi, int Do, int Ho, int Wo, double th, int erode,
+                            long long* counts, void* workspace, void* stream) {
+    if (!x || !counts || !workspace || planes < 1 || planes > 65535 || !(th == th)) return RS_ERR_ARG;
+    if (!dims_ok(Di, Hi, Wi) || !dims_ok(Do, Ho, Wo)) return RS_ERR_ARG;
+    ZoomGrid g;
+    g.Di = Di; g.Hi = Hi; g.Wi = Wi; g.Do = Do; g.Ho = Ho; g.Wo = Wo;
+    g.sz = Do > 1 ? (double)(Di - 1) / (double)(Do - 1) : 0.0;
+    g.sy = Ho > 1 ? (double)(Hi - 1) / (double)(Ho - 1) : 0.0;
+    g.sx = Wo > 1 ? (double)(Wi - 1) / (double)(Wo - 1) : 0.0;
+    g.identity = 0;                                      // unused: an unscaled axis has s == 1.0 and samples its own index
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* ws = (unsigned long long*)workspace;
+    const long nws = (long)planes * (DT_BINS + 1);
+    hipLaunchKernelGGL(detect_zero_kernel, dim3(grid_for(nws, GRID_CAP)), dim3(NT), 0, st, ws, nws);
+    const int tx = (Wo + DT_X - 1) / DT_X, ty = (Ho + DT_Y - 1) / DT_Y, tz = (Do + DT_Z - 1) / DT_Z;
+    const dim3 grid(tx * ty * tz, planes);
+    const long in_plane = (long)Di * Hi * Wi;
+    if (is_u8) {
+        const uint8_t* xb = (const uint8_t*)x;
+        if (erode) hipLaunchKernelGGL((detect_binary_kernel<uint8_t, true>), grid, dim3(NT), 0, st, xb, in_plane, g, th, tx, ty, ws);
+        else hipLaunchKernelGGL((detect_binary_kernel<uint8_t, false>), grid, dim3(NT), 0, st, xb, in_plane, g, th, tx, ty, ws);
+    } else {
+        const float* xf = (const float*)x;
+        if (erode) hipLaunchKernelGGL((detect_binary_kernel<float, true>), grid, dim3(NT), 0, st, xf, in_plane, g, th, tx, ty, ws);
+        else hipLaunchKernelGGL((detect_binary_kernel<float, false>), grid, dim3(NT), 0, st, xf, in_plane, g, th, tx, ty, ws);
+    }
+    hipLaunchKernelGGL(detect_binary_finalize_kernel, dim3(grid_for(planes, GRID_CAP)), dim3(NT), 0, st, (const unsigned long long*)ws, planes, counts);
     return rs_check_launch();
 }
 

@@ -129,6 +129,7 @@ _SIGS = {
     'rsuper_count': (c_int, [P, c_long, P, P]),
     'rsuper_detection_workspace_bytes': (c_long, [c_int]),
     'rsuper_detection': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P]),
+    'rsuper_detection_binary': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, P, P, P]),
     'rsuper_organ_mask_u8': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     'rsuper_organ_mask_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     'rsuper_largest_component_workspace_bytes': (c_long, [c_int, c_int, c_int]),

@@ -16,6 +16,7 @@ loss ops (training/losses_foundation.py; reference call sites rsuper_train/train
     torch.ops.rsuper.dilate_volume(vol, kernel_size) -> vol      torch.ops.rsuper.ball_search(x, diameter, sigma) -> key   (no derivative: masks / indices)
 prediction post-processing (inference/detection.py, inference/postprocess.py; no derivative):
     torch.ops.rsuper.detection_volumes(x, out_shape, thresholds, erode) -> (volumes, max_prob)
+    torch.ops.rsuper.detection_binary(x, out_shape, th, erode) -> counts
     torch.ops.rsuper.organ_mask(pred, lesion, organ_a, organ_b) -> planes       torch.ops.rsuper.largest_component(mask) -> mask
 spatial augmentation of the loader (training/augmentation.py; no derivative):
     torch.ops.rsuper.affine_crop(img, volumes, theta, out_size, offsets) -> (image crop, volume crops)
@@ -196,11 +197,12 @@ def _install_plain(group, ops):
     return _PLAIN_GROUPS[group]
 
 
-def install_postprocess_ops(detection_volumes, organ_mask, largest_component):
+def install_postprocess_ops(detection_volumes, detection_binary, organ_mask, largest_component):
     """The prediction post-processing operators of inference/detection.py and inference/postprocess.py (called at the end of postprocess.py): integer
     volumes, masks and labels have no derivative."""
     return _install_plain('postprocess', (
         ('detection_volumes', '(Tensor x, int[] out_shape, float[] thresholds, bool erode, Tensor? workspace=None) -> (Tensor, Tensor)', detection_volumes),
+        ('detection_binary', '(Tensor x, int[] out_shape, float th, bool erode, Tensor? workspace=None) -> Tensor', detection_binary),
         ('organ_mask', '(Tensor pred, int[] lesion, int[] organ_a, int[] organ_b) -> Tensor', organ_mask),
         ('largest_component', '(Tensor mask, Tensor? workspace=None) -> Tensor', largest_component)))
 

@@ -1,9 +1,10 @@
 """3-D inference helpers mirroring rsuper_train/inference: forward-only reuse of the HIP conv stack, plus the prediction
-post-processing of predict_abdomenatlas.py and the detection volumes of eval_AUC.py on the device, and the whole-case flow of predict_abdomenatlas.py
+post-processing of predict_abdomenatlas.py, the detection volumes of eval_AUC.py and test_with_reports.py on the device, and the whole-case flow of predict_abdomenatlas.py
 (preprocess -> prediction -> unpad_img -> resample_image_with_gpu -> postprocess_npz) under the reference's names."""
 from .utils import get_inference, split_idx  # noqa: F401
 from .inference3d import inference_whole_image, inference_sliding_window  # noqa: F401
 from .postprocess import prediction, postprocess_npz, keep_largest_component  # noqa: F401
-from .detection import detection, zoom_shape  # noqa: F401
+from .detection import detection, detection_binary, zoom_shape  # noqa: F401
 from .preprocess import normalize_ct, pad_to_training_size, unpad_img, preprocess_array  # noqa: F401
 from .resample import resample_image_with_gpu, predict_case  # noqa: F401
+from .scoring import score_case  # noqa: F401

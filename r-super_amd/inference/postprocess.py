@@ -14,7 +14,7 @@ import torch
 from ..hip import lib as _l
 from ..hip import ops as _ops  # noqa: F401  (imports hip/library.py in the order the op registration needs)
 from ..hip import library as _library
-from .detection import _detection_volumes_impl
+from .detection import _detection_volumes_impl, _detection_binary_impl
 from .inference3d import inference_sliding_window
 
 Z_LEN = 800          # prediction(): cases deeper than this are inferred in independent depth chunks (:190-194)
@@ -165,4 +165,4 @@ def prediction(model_list, img, args, tgt_organ=None, to_cpu=False):
     return label, raw
 
 
-_library.install_postprocess_ops(_detection_volumes_impl, _organ_mask_impl, _largest_component_impl)
+_library.install_postprocess_ops(_detection_volumes_impl, _detection_binary_impl, _organ_mask_impl, _largest_component_impl)
