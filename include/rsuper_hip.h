@@ -259,6 +259,22 @@ int rsuper_maxpool2_bwd(int dtype, const void* x, int ldx, const void* dy, int l
  * (RS_ERR_UNSUPPORTED otherwise).  Bit-identical to the two steps (both round the f32 sum of two bf16 values once). */
 int rsuper_maxpool2_bwd_add(int dtype, const void* x, int ldx, const void* dy, int lddy, const void* add, int lda, void* dx, int lddx,
                             int N, int D, int H, int W, int C, void* stream);
+/* rsuper_maxpool2_bwd_add with lazy gradients: where gm_y (gm_x) is given, dy (add) is not a finished gradient but the raw data gradient g of the
+ * convolution that read the pooled tensor (x) through InstanceNorm + ReLU, mr_* are that tensor's (mean, rstd) and gm_* the backward means
+ * (mean(g), mean(g x_n)), all [N][C][2]; the kernel applies the tail of rsuper_in_bwd_finalize to each vector as it reads it and rounds it to the
+ * storage type, so dx is bit for bit what rsuper_in_bwd_finalize followed by rsuper_maxpool2_bwd_add gives, without the launch and the tensor between
+ * them.  NULL gm_*: that gradient is final, as in rsuper_maxpool2_bwd_add.  RS_ERR_UNSUPPORTED where rsuper_maxpool2_bwd_lazy_plan does not answer 1
+ * (the caller then finalises the gradients itself). */
+int rsuper_maxpool2_bwd_lazy(int dtype, const void* x, int ldx, const void* dy, int lddy, const float* mr_y, const float* gm_y,
+                             const void* add, int lda, const float* mr_x, const float* gm_x, void* dx, int lddx,
+                             int N, int D, int H, int W, int C, void* stream);
+/* The one decision (csrc/lazy_tail_plan.hpp): 1 = the max-pool backward of an (N, D, H, W, C) input takes lazy gradients, 0 = the InstanceNorm backward
+ * tails run as launches of their own (odd sizes, rsuper_lazy_tails(0)), < 0 = bad arguments.  Pure host code. */
+int rsuper_maxpool2_bwd_lazy_plan(int dtype, int N, int D, int H, int W, int C);
+/* 1 (default): lazy gradients wherever the plans admit them; 0: none (A/B runs and tests: results are bit-identical); 2: wherever a fused kernel can take
+ * the launch, measured faster or not (tools/bench_lazy_tails.py).  RSUPER_LAZY_TAILS in the environment selects the value at start-up.  Any other v
+ * queries.  Returns the value in effect. */
+int rsuper_lazy_tails(int v);
 
 /* Stride-(2,2,2) down-sampling of down_block(pool=False) -- model/dim3/unet_utils.py:38-39 (`block(in_ch, out_ch,
  * stride=down_scale)`; conv_layers.py:29-38 with stride 2, padding 1).  The strided convolution is the stride-1 convolution
@@ -274,6 +290,14 @@ int rsuper_upsample_fwd(int dtype, const void* x, int ldx, void* y, int ldy, flo
                         int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, void* stream);
 int rsuper_upsample_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx,
                         int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, void* stream);
+/* rsuper_upsample_bwd of a lazy gradient: g is the raw data gradient of the convolution that read the up-sampled tensor u through InstanceNorm + ReLU,
+ * mr the statistics of u and gm the backward means ([N][C][2]); the load stage of the row-sharing kernel applies the tail of rsuper_in_bwd_finalize and
+ * its rounding, so dx is bit for bit what rsuper_in_bwd_finalize followed by rsuper_upsample_bwd gives.  bf16 only.  RS_ERR_UNSUPPORTED where
+ * rsuper_upsample_bwd_lazy_plan does not answer 1 or the kernel's tile tables do not hold the scale (the caller then finalises g itself). */
+int rsuper_upsample_bwd_lazy(int dtype, const void* g, int ldg, const void* u, int ldu, const float* mr, const float* gm, void* dx, int lddx,
+                             int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, void* stream);
+/* The one decision (csrc/lazy_tail_plan.hpp): 1 = lazy gradient, 0 = the tail runs as a launch of its own, < 0 = bad arguments.  Pure host code. */
+int rsuper_upsample_bwd_lazy_plan(int dtype, int N, int ID, int IH, int IW, int OD, int OH, int OW, int C);
 
 /* inconv.conv1 = nn.Conv3d(1, C, 3, padding=1, bias=False) -- model/dim3/unet_utils.py:14.  x: [N][D][H][W] f32. */
 int rsuper_stem_fwd(int dtype, const float* x, const float* w, void* y, int ldy, float* part,

@@ -22,6 +22,7 @@ static inline bool pack_range_ok(int mode, int na, int nb) { return mode != 1 ||
 
 #include "igemm_plan.hpp"      // which kernel / block width / statistics rows a 3x3x3 igemm launch gets: igemm_plan, s2_kernel (needs dt_ok, bn_ok)
 #include "wgrad_plan.hpp"      // which kernel / configuration / split count a 3x3x3 weight-gradient launch gets: wgrad_plan (needs dt_ok)
+#include "lazy_tail_plan.hpp"  // which InstanceNorm backward tails run inside the kernel that consumes them: lazy_pool_plan (needs dt_ok)
 
 // ---- optimiser: split the tensor list into kernel-argument sized chunks
 template <typename F>
@@ -434,6 +435,18 @@ int rsuper_maxpool2_bwd_add(int dtype, const void* x, int ldx, const void* dy, i
     PoolParams p = {x, ldx, (void*)dy, lddy, dx, lddx, nullptr, N, D, H, W, C, add, lda};
     return rs_launch_pool(p, dtype, 1, 1, ST(stream));
 }
+int rsuper_lazy_tails(int v) { return lazy_tails_variant(v); }
+int rsuper_maxpool2_bwd_lazy_plan(int dtype, int N, int D, int H, int W, int C) { return lazy_pool_plan(dtype, N, D, H, W, C); }
+int rsuper_maxpool2_bwd_lazy(int dtype, const void* x, int ldx, const void* dy, int lddy, const float* mr_y, const float* gm_y,
+                             const void* add, int lda, const float* mr_x, const float* gm_x, void* dx, int lddx,
+                             int N, int D, int H, int W, int C, void* stream) {
+    if (!dt_ok(dtype) || !x || !dy || !add || !dx || !ch_ok(C, ldx) || !ch_ok(C, lddy) || !ch_ok(C, lda) || !ch_ok(C, lddx) || C <= 0 || N <= 0 ||
+        D <= 0 || H <= 0 || W <= 0 || (gm_y && !mr_y) || (gm_x && !mr_x))
+        return RS_ERR_ARG;
+    if (lazy_pool_plan(dtype, N, D, H, W, C) != 1) return RS_ERR_UNSUPPORTED;      // the caller finalises the gradients and takes rsuper_maxpool2_bwd_add's path
+    PoolParams p = {x, ldx, (void*)dy, lddy, dx, lddx, nullptr, N, D, H, W, C, add, lda, gm_y ? mr_y : nullptr, gm_y, gm_x ? mr_x : nullptr, gm_x};
+    return rs_launch_pool(p, dtype, 1, 1, ST(stream));
+}
 
 int rsuper_subsample2_fwd(int dtype, const void* x, int ldx, void* y, int ldy, float* part, int blocks,
                           int N, int D, int H, int W, int C, void* stream) {
@@ -458,6 +471,17 @@ int rsuper_upsample_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx,
     if (!dt_ok(dtype) || !dy || !dx || !ch_ok(C, lddy) || !ch_ok(C, lddx)) return RS_ERR_ARG;
     UpParams p = {nullptr, 0, (void*)dy, lddy, dx, lddx, nullptr, N, ID, IH, IW, OD, OH, OW, C};
     return rs_launch_upsample(p, dtype, 1, 1, ST(stream));
+}
+int rsuper_upsample_bwd_lazy_plan(int dtype, int N, int ID, int IH, int IW, int OD, int OH, int OW, int C) {
+    return lazy_up_plan(dtype, N, ID, IH, IW, OD, OH, OW, C);
+}
+int rsuper_upsample_bwd_lazy(int dtype, const void* g, int ldg, const void* u, int ldu, const float* mr, const float* gm, void* dx, int lddx,
+                             int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, void* stream) {
+    if (!dt_ok(dtype) || !g || !u || !mr || !gm || !dx || !ch_ok(C, ldg) || !ch_ok(C, ldu) || !ch_ok(C, lddx) || C <= 0) return RS_ERR_ARG;
+    const int pl = lazy_up_plan(dtype, N, ID, IH, IW, OD, OH, OW, C);
+    if (pl < 0) return RS_ERR_ARG;
+    if (pl != 1) return RS_ERR_UNSUPPORTED;                      // the caller finalises g and calls rsuper_upsample_bwd
+    return rs_launch_upsample_bwd_lazy(g, ldg, u, ldu, mr, gm, dx, lddx, N, ID, IH, IW, OD, OH, OW, C, ST(stream));
 }
 int rsuper_stem_fwd(int dtype, const float* x, const float* w, void* y, int ldy, float* part,
                     int N, int D, int H, int W, int C, void* stream) {

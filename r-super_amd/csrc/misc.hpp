@@ -23,6 +23,10 @@ struct PoolParams {
     float* part;                   // forward: partial stats [N][blocks][C][2] or nullptr
     int N, D, H, W, C;             // input dims
     const void* add; int lda;      // max-pool backward: optional second gradient of x (the skip connection's) added to every voxel
+    // max-pool backward with lazy gradients: a gradient that arrives with its backward means gm is the raw data gradient g of an InstanceNorm'd
+    // convolution input, and the kernel applies the InstanceNorm backward tail while reading it (both [N][C][2]; nullptr: the gradient is final)
+    const float* mr_y; const float* gm_y;   // y lazy: (mean, rstd) of the pooled tensor, (mean(g), mean(g x_n))
+    const float* mr_x; const float* gm_x;   // add lazy: the same of x
 };
 
 struct UpParams {
@@ -76,5 +80,7 @@ int rs_launch_in_bwd(const InBwdParams& p, int dtype, hipStream_t st);
 int rs_launch_pool(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st);
 int rs_launch_subsample(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st);
 int rs_launch_upsample(const UpParams& p, int dtype, int bwd, int blocks, hipStream_t st);
+int rs_launch_upsample_bwd_lazy(const void* g, int ldg, const void* u, int ldu, const float* mr, const float* gm, void* dx, int lddx,
+                                int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, hipStream_t st);      // bf16 only
 int rs_launch_stem(const StemParams& p, int dtype, int wgrad, hipStream_t st);
 int rs_launch_head(const HeadParams& p, int dtype, int which, hipStream_t st);

@@ -86,6 +86,24 @@ __device__ __forceinline__ void block_channel_sums(const float* s1, const float*
 // The launch makes the grid stride a multiple of the channel-vector count whenever 256 % (C / KP) == 0, so a thread keeps its
 // channel slot for the whole loop: the 4 x KP per-channel constants are loaded once (they were 32 loads per 16-byte vector)
 // and the index math is 32-bit (the old size_t div / mod per vector cost more issue slots than the arithmetic).
+// One element of the tail.  in_bwd_finalize_kernel / in_bwd_finalize2_kernel and the kernels that apply the tail to a gradient they read
+// (maxpool_bwd_kernel's lazy operands) all call this, so the operation order -- and with it every bit of the result -- is one.
+__device__ __forceinline__ float in_bwd_tail(float g, float x, float mu, float rs, float m1, float m2) {
+    const float xn = (x - mu) * rs;
+    return rs * (g - m1 - xn * m2);
+}
+// f[] as a tensor of T would have held it between two launches: rounded to T.  f32 has no rounding; the empty asm there only keeps the compiler from
+// contracting the tail's last product into an addition of the consumer (the stored f32 value was the rounded product).
+template <typename T> __device__ __forceinline__ void round_as_stored(float* f) {
+    if constexpr (sizeof(T) == 4) {
+#pragma unroll
+        for (int j = 0; j < Elem<T>::KP; ++j) asm volatile("" : "+v"(f[j]));
+    } else {
+        const uint4 q = pack16<T>(f);
+        unpack16<T>(q, f);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void in_bwd_finalize_kernel(InBwdParams p) {
     constexpr int KP = Elem<T>::KP;
@@ -122,10 +140,7 @@ __global__ __launch_bounds__(256) void in_bwd_finalize_kernel(InBwdParams p) {
         unpack16<T>(gq, g);
         unpack16<T>(xq, x);
 #pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const float xn = (x[j] - mu[j]) * rs[j];
-            o[j] = rs[j] * (g[j] - m1[j] - xn * m2[j]);
-        }
+        for (int j = 0; j < KP; ++j) o[j] = in_bwd_tail(g[j], x[j], mu[j], rs[j], m1[j], m2[j]);
         if (a1p) {
             float a[KP];
             unpack16<T>(a1q, a);
@@ -186,10 +201,7 @@ __global__ __launch_bounds__(256) void in_bwd_finalize2_kernel(InBwdParams p, in
         unpack16<T>(gq[u], g);
         unpack16<T>(xq[u], x);
 #pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const float xn = (x[j] - mu[j]) * rs[j];
-            o[j] = rs[j] * (g[j] - m1[j] - xn * m2[j]);
-        }
+        for (int j = 0; j < KP; ++j) o[j] = in_bwd_tail(g[j], x[j], mu[j], rs[j], m1[j], m2[j]);
         if (a1p) {
             float a[KP];
             unpack16<T>(a1q[u], a);
@@ -300,16 +312,37 @@ __global__ __launch_bounds__(256) void maxpool_fwd2_kernel(PoolParams p) {
 }
 
 // dx = dy routed to the FIRST maximum in (d,h,w) scan order (ATen max_pool3d keeps the first `>`), else 0.
-template <typename T>
-__global__ void maxpool_bwd_kernel(PoolParams p) {
+// LAZY: either gradient may arrive as the raw data gradient g of the convolution that read the tensor through InstanceNorm + ReLU, with the norm's
+// statistics and the backward means: the InstanceNorm backward tail that a launch of in_bwd_finalize would have applied is applied to the vector as it
+// is read (bit 0: p.y is g of the pooled tensor, whose forward value is the maximum m; bit 1: p.add is g of x).  The value is rounded to T as the
+// finalised tensor stored it, so dx is bit for bit what the two launches gave.  LAZY = 0 is the kernel as it was.
+template <typename T, int LAZY>
+__global__ __launch_bounds__(LAZY ? 256 : 1024) void maxpool_bwd_kernel(PoolParams p) {
     constexpr int KP = Elem<T>::KP;
     const int CV = p.C / KP;
     const int n = blockIdx.y;
     const int OD = p.D / 2, OH = p.H / 2, OW = p.W / 2;
     const size_t total = (size_t)OD * OH * OW * CV;
+    // per-channel constants of the tails (mean, rstd, mean(g), mean(g x_n)): loaded once where the thread keeps its channel slot, as in in_bwd_finalize_kernel
+    constexpr int KY = (LAZY & 1) ? KP : 1, KX = (LAZY & 2) ? KP : 1;
+    [[maybe_unused]] float cy[4][KY], cx[4][KX];
+    [[maybe_unused]] auto constants = [&](int s) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const size_t o = ((size_t)n * p.C + s * KP + j) * 2;
+            if constexpr (LAZY & 1) { cy[0][j] = p.mr_y[o]; cy[1][j] = p.mr_y[o + 1]; cy[2][j] = p.gm_y[o]; cy[3][j] = p.gm_y[o + 1]; }
+            if constexpr (LAZY & 2) { cx[0][j] = p.mr_x[o]; cx[1][j] = p.mr_x[o + 1]; cx[2][j] = p.gm_x[o]; cx[3][j] = p.gm_x[o + 1]; }
+        }
+    };
+    const bool fixed_slot = LAZY != 0 && (blockDim.x % CV) == 0;    // the grid stride is a multiple of blockDim.x
+    if constexpr (LAZY != 0) {
+        const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (fixed_slot && i0 < total) constants((int)(i0 % CV));
+    }
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int s = (int)(i % CV); const int v = (int)(i / CV);
         const int ow = v % OW, oh = (v / OW) % OH, od = v / (OW * OH);
+        if constexpr (LAZY != 0) { if (!fixed_slot) constants(s); }
         float x[8][KP], m[KP], dy[KP];
 #pragma unroll
         for (int j = 0; j < KP; ++j) m[j] = -INFINITY;
@@ -321,6 +354,11 @@ __global__ void maxpool_bwd_kernel(PoolParams p) {
             for (int j = 0; j < KP; ++j) m[j] = fmaxf(m[j], x[k][j]);
         }
         unpack16<T>(*(const uint4*)((const T*)p.y + ((size_t)n * OD * OH * OW + v) * p.ldy + s * KP), dy);
+        if constexpr (LAZY & 1) {
+#pragma unroll
+            for (int j = 0; j < KP; ++j) dy[j] = in_bwd_tail(dy[j], m[j], cy[0][j], cy[1][j], cy[2][j], cy[3][j]);
+            round_as_stored<T>(dy);
+        }
         bool done[KP];
 #pragma unroll
         for (int j = 0; j < KP; ++j) done[j] = false;
@@ -337,6 +375,11 @@ __global__ void maxpool_bwd_kernel(PoolParams p) {
             if (p.add) {                                         // dx = scatter(dy) + add, rounded once: what autograd's accumulation of the two gradients stores
                 float a[KP];
                 unpack16<T>(*(const uint4*)((const T*)p.add + ((((size_t)n * p.D + d) * p.H + h) * p.W + w) * (size_t)p.lda + s * KP), a);
+                if constexpr (LAZY & 2) {
+#pragma unroll
+                    for (int j = 0; j < KP; ++j) a[j] = in_bwd_tail(a[j], x[k][j], cx[0][j], cx[1][j], cx[2][j], cx[3][j]);
+                    round_as_stored<T>(a);
+                }
 #pragma unroll
                 for (int j = 0; j < KP; ++j) o[j] += a[j];
             }
@@ -845,13 +888,20 @@ struct UpInParams {
     const void* g; int ldg;        // output gradient, channels-last on the (OD, OH, OW) grid
     void* dx; int lddx;
     int N, ID, IH, IW, OD, OH, OW, C;
+    // LAZY instantiations: g is the raw data gradient of the convolution that read the up-sampled tensor u through InstanceNorm + ReLU; the load stage
+    // applies the InstanceNorm backward tail (mr: statistics of u, gm: backward means, [N][C][2]) and rounds to bf16 before the row reduction
+    const void* u; int ldu;
+    const float* mr; const float* gm;
 };
 #ifndef UP4_SL
 #define UP4_SL 2
 #endif
 constexpr int UP4_ROWS = 16;       // candidate output rows of a pair of input indices (up_range of the first .. of the second): <= 2 * 2 / scale + 6
-template <int NT>
-__global__ __launch_bounds__(256, 3) void upsample_bwd4_kernel(UpInParams p, int nbx) {
+// LAZY: every loaded vector of g gets the tail of in_bwd_finalize (with the vector of u at the same voxel) and the rounding of the tensor that launch
+// would have written; weights and accumulation order are untouched, so dx is bit for bit that of in_bwd_finalize + this kernel.  The second operand
+// buffers and the 32 per-channel constants do not fit three blocks per CU: the lazy instantiations run two.
+template <int NT, bool LAZY>
+__global__ __launch_bounds__(256, LAZY ? 2 : 3) void upsample_bwd4_kernel(UpInParams p, int nbx) {
     typedef bf16_t T;
     constexpr int CPT = 8, NWD = CPT / 2;                        // channels per thread (one 16-byte vector), 32-bit words of it
     constexpr int SL = UP4_SL;                                   // row slots: SL - 1 rows of loads in flight behind the one being reduced
@@ -931,6 +981,22 @@ __global__ __launch_bounds__(256, 3) void upsample_bwd4_kernel(UpInParams p, int
 #pragma unroll
         for (int k = 0; k < CPT; ++k) acc[i][k] = 0.f;
     uint4 gq[SL][NT];
+    // lazy: the same taps of u, and the thread's tail constants (its channel slot is fixed)
+    const uint32_t urow = LAZY ? (uint32_t)p.ldu * 2u : 0u;
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(LAZY ? (void*)((const T*)p.u + (size_t)n * ovox * p.ldu) : nullptr, 0,
+                                                                         LAZY ? ovox * urow : 0u, 0x00020000);
+    [[maybe_unused]] uint32_t uoff[LAZY ? NT : 1];
+    [[maybe_unused]] uint4 uq[LAZY ? SL : 1][LAZY ? NT : 1];
+    [[maybe_unused]] float cmu[LAZY ? CPT : 1], crs[LAZY ? CPT : 1], cm1[LAZY ? CPT : 1], cm2[LAZY ? CPT : 1];
+    if constexpr (LAZY) {
+#pragma unroll
+        for (int c = 0; c < NT; ++c) uoff[c] = (uint32_t)(wlo + (wc[c] != 0.f ? c : 0)) * urow + (uint32_t)s * 16u;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            const size_t o = ((size_t)n * p.C + s * CPT + k) * 2;
+            cmu[k] = p.mr[o]; crs[k] = p.mr[o + 1]; cm1[k] = p.gm[o]; cm2[k] = p.gm[o + 1];
+        }
+    }
     int ia = 0, ib = 0;                                          // (a, b) of the next row to issue
     auto issue = [&](int slot) {
         const uint32_t row = (uint32_t)__builtin_amdgcn_readfirstlane(((od0 + ia) * p.OH + (oh0 + ib)) * p.OW);
@@ -938,6 +1004,10 @@ __global__ __launch_bounds__(256, 3) void upsample_bwd4_kernel(UpInParams p, int
         for (int c = 0; c < NT; ++c) {
             const auto q = __builtin_amdgcn_raw_buffer_load_b128(grs, goff[c], row * grow, 0);
             gq[slot][c] = make_uint4(q[0], q[1], q[2], q[3]);
+            if constexpr (LAZY) {
+                const auto r = __builtin_amdgcn_raw_buffer_load_b128(urs, uoff[c], row * urow, 0);
+                uq[slot][c] = make_uint4(r[0], r[1], r[2], r[3]);
+            }
         }
         if (++ib == rh) { ib = 0; ++ia; }
     };
@@ -955,7 +1025,16 @@ __global__ __launch_bounds__(256, 3) void upsample_bwd4_kernel(UpInParams p, int
 #pragma unroll
             for (int c = 0; c < NT; ++c) {
                 const f32x2_t w2 = {wc[c], wc[c]};
-                const uint32_t wq[4] = {gq[h][c].x, gq[h][c].y, gq[h][c].z, gq[h][c].w};
+                uint4 gv = gq[h][c];
+                if constexpr (LAZY) {
+                    float g[CPT], x[CPT];
+                    unpack16<T>(gv, g);
+                    unpack16<T>(uq[h][c], x);
+#pragma unroll
+                    for (int k = 0; k < CPT; ++k) g[k] = in_bwd_tail(g[k], x[k], cmu[k], crs[k], cm1[k], cm2[k]);
+                    gv = pack16<T>(g);                           // the rounding of the finalised tensor
+                }
+                const uint32_t wq[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
                 for (int j = 0; j < NWD; ++j) {
                     const f32x2_t v2 = {__uint_as_float(wq[j] << 16), __uint_as_float(wq[j] & 0xffff0000u)};
@@ -1509,8 +1588,15 @@ int rs_launch_pool(const PoolParams& p, int dtype, int bwd, int blocks, hipStrea
         const size_t items = (size_t)(p.D / 2) * (p.H / 2) * (p.W / 2) * CV;
         int b = rs_elem_blocks(items), threads = 256;
         if (rs_glue_variant(-1) && (size_t)b * p.N < 512) { threads = 64; b = (int)((items + 63) / 64); }      // small volumes: one wave per block, four times the CUs
-        if (dtype == RS_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(b, p.N), dim3(threads), 0, st, p);
-        else hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(b, p.N), dim3(threads), 0, st, p);
+        const int lazy = (p.gm_y ? 1 : 0) | (p.gm_x ? 2 : 0);
+        if ((p.gm_y && !p.mr_y) || (p.gm_x && (!p.mr_x || !p.add))) return RS_ERR_ARG;
+#define RS_POOL_BWD(LZ)                                                                                                   \
+        case LZ:                                                                                                          \
+            if (dtype == RS_F32) hipLaunchKernelGGL((maxpool_bwd_kernel<float, LZ>), dim3(b, p.N), dim3(threads), 0, st, p);   \
+            else hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, LZ>), dim3(b, p.N), dim3(threads), 0, st, p);             \
+            break;
+        switch (lazy) { RS_POOL_BWD(0) RS_POOL_BWD(1) RS_POOL_BWD(2) RS_POOL_BWD(3) }
+#undef RS_POOL_BWD
     }
     return rs_check_launch();
 }
@@ -1534,10 +1620,13 @@ int rs_launch_subsample(const PoolParams& p, int dtype, int bwd, int blocks, hip
 }
 
 // trilinear backward on the row-sharing kernel (bf16); RS_ERR_UNSUPPORTED for scales its tile tables do not hold (the caller runs upsample_bwd2 then)
-static int launch_upsample_bwd4(const void* g, int ldg, void* dx, int lddx, int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, hipStream_t st) {
+// lz (or nullptr): the lazy operands (u, ldu, mr, gm of UpInParams) -- g is then a raw data gradient and the kernel applies its InstanceNorm backward tail
+static int launch_upsample_bwd4(const void* g, int ldg, void* dx, int lddx, int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, hipStream_t st,
+                                const UpInParams* lz = nullptr) {
     static const bool off = getenv("RSUPER_UPSAMPLE_BWD4") && atoi(getenv("RSUPER_UPSAMPLE_BWD4")) == 0;
     if (off || (C % 8) || N > 65535) return RS_ERR_UNSUPPORTED;
     if ((size_t)OD * OH * OW * (size_t)ldg * 2 >= 0xFFFFFFFFull) return RS_ERR_UNSUPPORTED;                    // 32-bit byte offsets
+    if (lz && (size_t)OD * OH * OW * (size_t)lz->ldu * 2 >= 0xFFFFFFFFull) return RS_ERR_UNSUPPORTED;
     // the table sizes depend on the shape only: remembered per (ID, IH, IW, OD, OH, OW) (the host loops cost a few microseconds per call otherwise)
     struct Memo { int k[6]; int ok, nmax; };
     static thread_local Memo memo[8] = {};
@@ -1556,11 +1645,27 @@ static int launch_upsample_bwd4(const void* g, int ldg, void* dx, int lddx, int 
     const int nmax = hit->nmax;
     if (nmax > 6) return RS_ERR_UNSUPPORTED;
     UpInParams p = {g, ldg, dx, lddx, N, ID, IH, IW, OD, OH, OW, C};
+    if (lz) { p.u = lz->u; p.ldu = lz->ldu; p.mr = lz->mr; p.gm = lz->gm; }
     const int nbx = (IW * (C / 8) + 255) / 256;
     const unsigned blocks = (unsigned)(((ID + 1) / 2) * ((IH + 1) / 2) * nbx);
-    if (nmax <= 4) hipLaunchKernelGGL((upsample_bwd4_kernel<4>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
-    else hipLaunchKernelGGL((upsample_bwd4_kernel<6>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
+    if (lz) {
+        if (nmax <= 4) hipLaunchKernelGGL((upsample_bwd4_kernel<4, true>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
+        else hipLaunchKernelGGL((upsample_bwd4_kernel<6, true>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
+    } else {
+        if (nmax <= 4) hipLaunchKernelGGL((upsample_bwd4_kernel<4, false>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
+        else hipLaunchKernelGGL((upsample_bwd4_kernel<6, false>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
+    }
     return rs_check_launch();
+}
+
+// trilinear backward of a lazy gradient: the row-sharing kernel or RS_ERR_UNSUPPORTED (the caller finalises g and calls rs_launch_upsample)
+int rs_launch_upsample_bwd_lazy(const void* g, int ldg, const void* u, int ldu, const float* mr, const float* gm, void* dx, int lddx,
+                                int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, hipStream_t st) {
+    static const bool v1 = getenv("RSUPER_UPSAMPLE_V1") != nullptr;
+    if (v1) return RS_ERR_UNSUPPORTED;
+    UpInParams lz = {};
+    lz.u = u; lz.ldu = ldu; lz.mr = mr; lz.gm = gm;
+    return launch_upsample_bwd4(g, ldg, dx, lddx, N, ID, IH, IW, OD, OH, OW, C, st, &lz);
 }
 
 int rs_launch_upsample(const UpParams& p, int dtype, int bwd, int blocks, hipStream_t st) {

@@ -59,6 +59,11 @@ _SIGS = {
     'rsuper_maxpool2_fwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_bwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_bwd_add': (c_int, [c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'rsuper_maxpool2_bwd_lazy': (c_int, [c_int, P, c_int, P, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'rsuper_maxpool2_bwd_lazy_plan': (c_int, [c_int] * 6),
+    'rsuper_lazy_tails': (c_int, [c_int]),
+    'rsuper_upsample_bwd_lazy': (c_int, [c_int, P, c_int, P, c_int, P, P, P, c_int] + [c_int] * 8 + [P]),
+    'rsuper_upsample_bwd_lazy_plan': (c_int, [c_int] * 9),
     'rsuper_subsample2_fwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'rsuper_subsample2_bwd': (c_int, [c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'rsuper_upsample_fwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int] + [c_int] * 8 + [P]),

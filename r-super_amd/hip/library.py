@@ -6,6 +6,9 @@ registered as custom HIP ops behind the repo's existing model/ and training/ int
     torch.ops.rsuper.basic_block(xa, mra, xb, mrb, w1, w2, ws, pack_bufs, pack_bns, stride) -> (out, mr_out)
     torch.ops.rsuper.maxpool2(x) -> (y, mr)                    torch.ops.rsuper.upsample_trilinear(x, size) -> (y, mr)
     torch.ops.rsuper.maxpool2_skip(x) -> (y, mr, x)            (x again as the skip connection: both gradients of x meet in one backward launch)
+    torch.ops.rsuper.maxpool2_skip_lazy(x, mrx) -> (y, mr, x, mrx)   (both statistics differentiable: the blocks that read them hand their gradients over
+                                                                without the InstanceNorm backward tail, which the pool's backward kernel applies)
+    torch.ops.rsuper.upsample_trilinear_lazy(x, size) -> (y, mr)     (the same for the block that reads the up-sampled tensor)
     torch.ops.rsuper.stem_conv(img, w, dtype) -> (y, mr)       torch.ops.rsuper.head_conv(x, w, b) -> logits
     torch.ops.rsuper.conv3(x, w) -> y                          torch.ops.rsuper.channel_norm(x, eps, relu) -> y
     torch.ops.rsuper.depthwise_conv3(x, w) -> y                torch.ops.rsuper.squeeze_excite(x, w1, b1, w2, b2) -> y
@@ -134,7 +137,9 @@ def install():
          _bb_fn_args, _bb_apply_args),
         ('MaxPoolFn', 'maxpool2', '(Tensor x) -> (Tensor, Tensor)', None, None),
         ('MaxPoolSkipFn', 'maxpool2_skip', '(Tensor(a) x) -> (Tensor, Tensor, Tensor(a))', None, None),
+        ('MaxPoolSkipLazyFn', 'maxpool2_skip_lazy', '(Tensor(a) x, Tensor(b) mrx) -> (Tensor, Tensor, Tensor(a), Tensor(b))', None, None),
         ('UpsampleFn', 'upsample_trilinear', '(Tensor x, int[] size) -> (Tensor, Tensor)', lambda x, size: (x, tuple(size)), None),
+        ('UpsampleLazyFn', 'upsample_trilinear_lazy', '(Tensor x, int[] size) -> (Tensor, Tensor)', lambda x, size: (x, tuple(size)), None),
         ('StemFn', 'stem_conv', '(Tensor img, Tensor w, ScalarType dtype) -> (Tensor, Tensor)', None, None),
         ('HeadFn', 'head_conv', '(Tensor x, Tensor w, Tensor b) -> Tensor', None, None),
         ('Conv3Fn', 'conv3', '(Tensor x, Tensor w) -> Tensor', None, None),

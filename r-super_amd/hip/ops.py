@@ -711,12 +711,26 @@ class BasicBlockFn(torch.autograd.Function):
         # both weight gradients of the block: one reduction launch, slabs still hot in L2.  It also finalises the InstanceNorm-backward rows of this
         # data gradient, so it runs BEFORE the InstanceNorm-backward tails.
         gm0 = flush_wgrad_reduces(stats=stats)
+        # A source whose statistics tensor wants a gradient is handed on LAZY: its tail is not launched, the raw g goes out as the source's gradient and the
+        # backward means as the "gradient" of the statistics.  Only a node that applies the tail inside its own backward kernel gives out such a statistics
+        # tensor (MaxPoolSkipLazyFn, UpsampleLazyFn); a block that adds dOut in its tail (no shortcut) finalises as ever and returns no means.
+        lazy_a, lazy_b = ctx.needs_input_grad[1] and has_sc, xb is not None and ctx.needs_input_grad[3]
         if xb is None:
-            dxa, dxb = in_bwd_finalize(g0s[0], sa, gm0[0], Ca, add1=None if has_sc else dout), None
+            gma, gmb = gm0[0], None
         else:
             gma, gmb = gm0 if len(gm0) == 2 else gm0[0]       # one table per launch, or the joint launch's table split at Ca
-            dxa, dxb = in_bwd_finalize(g0s[0], sa, gma, Ca), in_bwd_finalize(g0s[1], sb, gmb, Cb)
-        return dxa, None, dxb, None, dw1, dw2, dws, None, None
+
+        def raw(g):
+            return g.t if g.C == g.ld else g.t[..., g.off:g.off + g.C]
+        if lazy_a:
+            dxa = raw(g0s[0])
+        else:
+            dxa, gma = in_bwd_finalize(g0s[0], sa, gma, Ca, add1=None if has_sc else dout), None
+        if lazy_b:
+            dxb = raw(g0s[1])
+        else:
+            dxb, gmb = (None if xb is None else in_bwd_finalize(g0s[1], sb, gmb, Cb)), None
+        return dxa, gma, dxb, gmb, dw1, dw2, dws, None, None
 
 
 _BB = BasicBlockFn        # the class itself: `BasicBlockFn` is rebound to the registered dispatcher op below
@@ -727,19 +741,43 @@ def _stat_blocks(ovox):
     return max(1, min(2048, ovox // 64))
 
 
+def _maxpool_fwd(x):
+    _chk_act(x)
+    N, D, H, W, C = x.shape
+    OD, OH, OW = D // 2, H // 2, W // 2
+    y = torch.empty((N, OD, OH, OW, C), device=x.device, dtype=x.dtype)
+    blocks = _stat_blocks(OD * OH * OW)
+    part = torch.empty((N, blocks, C, 2), device=x.device, dtype=torch.float32)
+    _l.check(_L().rsuper_maxpool2_fwd(_DT[x.dtype], _ptr(x), C, _ptr(y), C, _ptr(part), blocks, N, D, H, W, C, _stream()), 'maxpool2_fwd')
+    return y, stats_finalize(part, OD * OH * OW)
+
+
+def _maxpool_bwd(x, dy):
+    dy = dy.contiguous()
+    N, D, H, W, C = x.shape
+    dx = torch.empty_like(x)
+    _l.check(_L().rsuper_maxpool2_bwd(_DT[x.dtype], _ptr(x), C, _ptr(dy), C, _ptr(dx), C, N, D, H, W, C, _stream()), 'maxpool2_bwd')
+    return dx
+
+
+def _maxpool_bwd_add(x, dy, dskip):
+    """Both gradients of x in one launch (rsuper_maxpool2_bwd_add); odd sizes: the two steps."""
+    N, D, H, W, C = x.shape
+    dy, dskip = dy.contiguous(), dskip.contiguous()
+    dx = torch.empty_like(x)
+    rc = _L().rsuper_maxpool2_bwd_add(_DT[x.dtype], _ptr(x), C, _ptr(dy), C, _ptr(dskip), C, _ptr(dx), C, N, D, H, W, C, _stream())
+    if rc == 3:
+        return _maxpool_bwd(x, dy) + dskip
+    _l.check(rc, 'maxpool2_bwd_add')
+    return dx
+
+
 class MaxPoolFn(torch.autograd.Function):
     """nn.MaxPool3d(2) (model/dim3/unet_utils.py:35-37) + statistics of the pooled tensor."""
 
     @staticmethod
     def forward(ctx, x):
-        _chk_act(x)
-        N, D, H, W, C = x.shape
-        OD, OH, OW = D // 2, H // 2, W // 2
-        y = torch.empty((N, OD, OH, OW, C), device=x.device, dtype=x.dtype)
-        blocks = _stat_blocks(OD * OH * OW)
-        part = torch.empty((N, blocks, C, 2), device=x.device, dtype=torch.float32)
-        _l.check(_L().rsuper_maxpool2_fwd(_DT[x.dtype], _ptr(x), C, _ptr(y), C, _ptr(part), blocks, N, D, H, W, C, _stream()), 'maxpool2_fwd')
-        mr = stats_finalize(part, OD * OH * OW)
+        y, mr = _maxpool_fwd(x)
         ctx.save_for_backward(x)
         ctx.mark_non_differentiable(mr)
         ctx.set_materialize_grads(False)
@@ -748,11 +786,7 @@ class MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _unused):
         (x,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        N, D, H, W, C = x.shape
-        dx = torch.empty_like(x)
-        _l.check(_L().rsuper_maxpool2_bwd(_DT[x.dtype], _ptr(x), C, _ptr(dy), C, _ptr(dx), C, N, D, H, W, C, _stream()), 'maxpool2_bwd')
-        return dx
+        return _maxpool_bwd(x, dy)
 
 
 _MaxPoolFn = MaxPoolFn          # the class itself (hip/library.py rebinds `MaxPoolFn` to the dispatcher entry)
@@ -775,14 +809,63 @@ class MaxPoolSkipFn(torch.autograd.Function):
         if dskip is None:
             return _MaxPoolFn.backward(ctx, dy, None)
         (x,) = ctx.saved_tensors
+        return _maxpool_bwd_add(x, dy, dskip)
+
+
+def maxpool_lazy_plan(x):
+    """Whether the max-pool backward of x takes lazy gradients (rsuper_maxpool2_bwd_lazy_plan, csrc/lazy_tail_plan.hpp: the one decision)."""
+    N, D, H, W, C = x.shape
+    return x.dtype in _DT and _L().rsuper_maxpool2_bwd_lazy_plan(_DT[x.dtype], N, D, H, W, C) == 1
+
+
+def _rows(g):
+    """(tensor, row stride) of a gradient (N, D, H, W, C) for a kernel that takes a leading dimension: a channel slice of a wider channels-last tensor
+    (the joint data gradient of a two-source block) is read in place, anything else contiguous."""
+    N, D, H, W, C = g.shape
+    ld = g.stride(3)
+    if g.stride(4) == 1 and ld >= C and ld % 8 == 0 and g.stride() == (D * H * W * ld, H * W * ld, W * ld, ld, 1):
+        return g, ld
+    return g.contiguous(), C
+
+
+def _finalized(g, x, mr, gm):
+    """A gradient as MaxPoolSkipLazyFn.backward receives it -> the finished gradient: gm is None for a finished one, else g is raw and gets its tail."""
+    if g is None or gm is None:
+        return g
+    return in_bwd_finalize(Src(g.contiguous()), Src(x, mr=mr), gm.contiguous(), g.shape[-1])
+
+
+class MaxPoolSkipLazyFn(torch.autograd.Function):
+    """MaxPoolSkipFn for the UNet's blocks, taking both gradients LAZY: (x, statistics of x) -> (pooled, its statistics, x again, the statistics of x
+    again).  Both statistics outputs are differentiable: a BasicBlockFn that reads a tensor with such statistics skips the InstanceNorm backward tail of
+    that source and returns the raw data gradient g, with the backward means as the statistics' "gradient", and this node's backward kernel applies the
+    tail as it reads g (rsuper_maxpool2_bwd_lazy: 8 launches and 8 tensors fewer per UNet step, bit-identical).  A gradient that arrives without means is
+    a finished one; shapes the plan refuses and a missing gradient finalise first and take MaxPoolSkipFn's path."""
+
+    @staticmethod
+    def forward(ctx, x, mrx):
+        y, mr = _maxpool_fwd(x)
+        ctx.save_for_backward(x, mrx, y, mr)
+        ctx.set_materialize_grads(False)
+        return y, mr, x.view_as(x), mrx.view_as(mrx)
+
+    @staticmethod
+    def backward(ctx, dy, gmy, dskip, gmx):
+        x, mrx, y, mry = ctx.saved_tensors
         N, D, H, W, C = x.shape
-        dy, dskip = dy.contiguous(), dskip.contiguous()
-        dx = torch.empty_like(x)
-        rc = _L().rsuper_maxpool2_bwd_add(_DT[x.dtype], _ptr(x), C, _ptr(dy), C, _ptr(dskip), C, _ptr(dx), C, N, D, H, W, C, _stream())
-        if rc == 3:                                              # odd sizes: the two steps
-            return _MaxPoolFn.backward(ctx, dy, None) + dskip
-        _l.check(rc, 'maxpool2_bwd_add')
-        return dx
+        if dy is not None and dskip is not None and (gmy is not None or gmx is not None):
+            (dy, lddy), (dskip, lda) = _rows(dy), _rows(dskip)
+            gmy, gmx = (None if gmy is None else gmy.contiguous()), (None if gmx is None else gmx.contiguous())
+            dx = torch.empty_like(x)
+            rc = _L().rsuper_maxpool2_bwd_lazy(_DT[x.dtype], _ptr(x), C, _ptr(dy), lddy, _ptr(mry), _ptr(gmy), _ptr(dskip), lda, _ptr(mrx), _ptr(gmx),
+                                               _ptr(dx), C, N, D, H, W, C, _stream())
+            if rc != 3:
+                _l.check(rc, 'maxpool2_bwd_lazy')
+                return dx, None
+        dy, dskip = _finalized(dy, y, mry, gmy), _finalized(dskip, x, mrx, gmx)
+        if dy is None:
+            return dskip, None
+        return (_maxpool_bwd(x, dy) if dskip is None else _maxpool_bwd_add(x, dy, dskip)), None
 
 
 def subsample2(x, with_stats=True):
@@ -803,20 +886,33 @@ def subsample2_scatter(dy, out, off, dims):
     _l.check(_L().rsuper_subsample2_bwd(_DT[dy.dtype], _ptr(dy), C, _ptr(out, off), out.shape[-1], N, D, H, W, C, _stream()), 'subsample2_bwd')
 
 
+def _upsample_fwd(x, size):
+    _chk_act(x)
+    N, ID, IH, IW, C = x.shape
+    OD, OH, OW = size
+    y = torch.empty((N, OD, OH, OW, C), device=x.device, dtype=x.dtype)
+    blocks = _stat_blocks(OD * OH * OW)
+    part = torch.empty((N, blocks, C, 2), device=x.device, dtype=torch.float32)
+    _l.check(_L().rsuper_upsample_fwd(_DT[x.dtype], _ptr(x), C, _ptr(y), C, _ptr(part), blocks, N, ID, IH, IW, OD, OH, OW, C, _stream()),
+              'upsample_fwd')
+    return y, stats_finalize(part, OD * OH * OW)
+
+
+def _upsample_bwd(in_shape, dy):
+    dy = dy.contiguous()
+    N, ID, IH, IW, C = in_shape
+    OD, OH, OW = dy.shape[1:4]
+    dx = torch.empty(in_shape, device=dy.device, dtype=dy.dtype)
+    _l.check(_L().rsuper_upsample_bwd(_DT[dy.dtype], _ptr(dy), C, _ptr(dx), C, N, ID, IH, IW, OD, OH, OW, C, _stream()), 'upsample_bwd')
+    return dx
+
+
 class UpsampleFn(torch.autograd.Function):
     """F.interpolate(x, size, mode='trilinear', align_corners=True) (model/dim3/unet_utils.py:69)."""
 
     @staticmethod
     def forward(ctx, x, size):
-        _chk_act(x)
-        N, ID, IH, IW, C = x.shape
-        OD, OH, OW = size
-        y = torch.empty((N, OD, OH, OW, C), device=x.device, dtype=x.dtype)
-        blocks = _stat_blocks(OD * OH * OW)
-        part = torch.empty((N, blocks, C, 2), device=x.device, dtype=torch.float32)
-        _l.check(_L().rsuper_upsample_fwd(_DT[x.dtype], _ptr(x), C, _ptr(y), C, _ptr(part), blocks, N, ID, IH, IW, OD, OH, OW, C, _stream()),
-                  'upsample_fwd')
-        mr = stats_finalize(part, OD * OH * OW)
+        y, mr = _upsample_fwd(x, size)
         ctx.in_shape = tuple(x.shape)
         ctx.mark_non_differentiable(mr)
         ctx.set_materialize_grads(False)
@@ -824,12 +920,45 @@ class UpsampleFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _unused):
-        dy = dy.contiguous()
-        N, ID, IH, IW, C = ctx.in_shape
-        OD, OH, OW = dy.shape[1:4]
-        dx = torch.empty(ctx.in_shape, device=dy.device, dtype=dy.dtype)
-        _l.check(_L().rsuper_upsample_bwd(_DT[dy.dtype], _ptr(dy), C, _ptr(dx), C, N, ID, IH, IW, OD, OH, OW, C, _stream()), 'upsample_bwd')
-        return dx, None
+        return _upsample_bwd(ctx.in_shape, dy), None
+
+
+def upsample_lazy_plan(x, size):
+    """Whether the trilinear backward of x -> size takes a lazy gradient (rsuper_upsample_bwd_lazy_plan, csrc/lazy_tail_plan.hpp: the one decision)."""
+    N, ID, IH, IW, C = x.shape
+    return x.dtype in _DT and _L().rsuper_upsample_bwd_lazy_plan(_DT[x.dtype], N, ID, IH, IW, *size, C) == 1
+
+
+class UpsampleLazyFn(torch.autograd.Function):
+    """UpsampleFn for the UNet's up_block, taking its gradient LAZY: the statistics output is differentiable, so the BasicBlockFn that reads the up-sampled
+    tensor u skips that source's InstanceNorm backward tail and returns the raw data gradient g with the backward means as the statistics' "gradient";
+    the trilinear backward kernel applies the tail in its load stage (rsuper_upsample_bwd_lazy, bit-identical).  A gradient that arrives without means
+    is a finished one; a launch the kernel refuses finalises first and takes UpsampleFn's path."""
+
+    @staticmethod
+    def forward(ctx, x, size):
+        y, mr = _upsample_fwd(x, size)
+        ctx.in_shape = tuple(x.shape)
+        ctx.save_for_backward(y, mr)
+        ctx.set_materialize_grads(False)
+        return y, mr
+
+    @staticmethod
+    def backward(ctx, dy, gm):
+        if dy is None:
+            return None, None
+        u, mr = ctx.saved_tensors
+        if gm is not None:
+            N, ID, IH, IW, C = ctx.in_shape
+            OD, OH, OW = u.shape[1:4]
+            (g, ldg), gm = _rows(dy), gm.contiguous()
+            dx = torch.empty(ctx.in_shape, device=u.device, dtype=u.dtype)
+            rc = _L().rsuper_upsample_bwd_lazy(_DT[u.dtype], _ptr(g), ldg, _ptr(u), C, _ptr(mr), _ptr(gm), _ptr(dx), C,
+                                               N, ID, IH, IW, OD, OH, OW, C, _stream())
+            if rc != 3:
+                _l.check(rc, 'upsample_bwd_lazy')
+                return dx, None
+        return _upsample_bwd(ctx.in_shape, _finalized(dy, u, mr, gm)), None
 
 
 # ------------------------------------------------------------------------------------------------ stem / head

@@ -59,13 +59,15 @@ class UNet(nn.Module):
         _lib.require_device()
         dt = self._dtype()
         x1, m1 = self.inc(x, dt)
-        x2, m2, x1 = self.down1(x1, m1, True)      # x_k comes back as the skip tensor: both of its gradients meet in the pooling layer's backward
-        x3, m3, x2 = self.down2(x2, m2, True)
-        x4, m4, x3 = self.down3(x3, m3, True)
-        x5, m5, x4 = self.down4(x4, m4, True)
-        o, mo = self.up1(x5, m5, x4, m4)
-        o, mo = self.up2(o, mo, x3, m3)
-        o, mo = self.up3(o, mo, x2, m2)
-        o, mo = self.up4(o, mo, x1, m1)
+        # x_k comes back as the skip tensor: both of its gradients meet in the pooling layer's backward.  s_k: the statistics that go with the skip (those
+        # of x_k, as the pooling layer hands them out: its backward kernel then also applies the InstanceNorm backward tails of both gradients)
+        x2, m2, x1, s1 = self.down1(x1, m1, True, True)
+        x3, m3, x2, s2 = self.down2(x2, m2, True, True)
+        x4, m4, x3, s3 = self.down3(x3, m3, True, True)
+        x5, m5, x4, s4 = self.down4(x4, m4, True, True)
+        o, mo = self.up1(x5, m5, x4, s4)
+        o, mo = self.up2(o, mo, x3, s3)
+        o, mo = self.up3(o, mo, x2, s2)
+        o, mo = self.up4(o, mo, x1, s1)
         logits = ops.HeadFn.apply(o, self.outc.weight, self.outc.bias)
         return {'segmentation': logits}

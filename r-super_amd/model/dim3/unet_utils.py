@@ -10,7 +10,11 @@ from ...hip import ops
 class _Pool(nn.Module):
     """Occupies index 0 of down_block.conv like nn.MaxPool3d does in the reference (unet_utils.py:36)."""
 
-    def forward(self, x, with_skip=False):
+    def forward(self, x, with_skip=False, mr=None):
+        """mr (with_skip): the statistics of x, to take both gradients of x lazy -- the blocks that read the pooled tensor and the skip then leave their
+        InstanceNorm backward tails to the pool's backward kernel (ops.MaxPoolSkipLazyFn); returns the skip's statistics as a fourth value."""
+        if mr is not None:
+            return ops.MaxPoolSkipLazyFn.apply(x, mr)
         return ops.MaxPoolSkipFn.apply(x) if with_skip else ops.MaxPoolFn.apply(x)
 
 
@@ -40,19 +44,27 @@ class down_block(nn.Module):
             layers.append(block(out_ch, out_ch, kernel_size=kernel_size, norm=norm))
         self.conv = nn.Sequential(*layers)
 
-    def forward(self, x, mr, with_skip=False):
+    def forward(self, x, mr, with_skip=False, lazy=False):
         """with_skip: also return the input as the tensor to hand to the matching up_block (pooling layers only: its gradient is then added inside
-        the max-pool backward kernel; with a strided first block the input itself is returned)."""
+        the max-pool backward kernel; with a strided first block the input itself is returned).
+        lazy (with with_skip): a fourth value, the statistics to hand to the up_block with the skip.  Where the pooling layer's backward takes lazy
+        gradients (ops.maxpool_lazy_plan) they are its differentiable alias of mr, and so are the pooled tensor's: the first block here and the first
+        block of the up_block then skip their InstanceNorm backward tails.  Elsewhere (pool=False, odd sizes, no gradient) they are mr itself."""
         blocks = list(self.conv)
-        skip = x
+        skip, mr_skip = x, mr
         if self.pool:
             if with_skip and torch.is_grad_enabled() and x.requires_grad:
-                x, mr, skip = blocks[0](x, True)
+                if lazy and ops.maxpool_lazy_plan(x):
+                    x, mr, skip, mr_skip = blocks[0](x, True, mr)
+                else:
+                    x, mr, skip = blocks[0](x, True)
             else:
                 x, mr = blocks[0](x)
             blocks = blocks[1:]
         for blk in blocks:
             x, mr = blk(x, mr)
+        if with_skip and lazy:
+            return x, mr, skip, mr_skip
         return (x, mr, skip) if with_skip else (x, mr)
 
 
@@ -67,7 +79,10 @@ class up_block(nn.Module):
     def forward(self, x1, mr1, x2, mr2):
         """x1: coarse map, x2: skip.  cat([x2, x1]) (unet_utils.py:71) is never materialised: the first block
         reads both sources."""
-        up, mru = ops.UpsampleFn.apply(x1, tuple(x2.shape[1:4]))
+        size = tuple(x2.shape[1:4])
+        # where the trilinear backward takes a lazy gradient, the first block leaves the InstanceNorm backward tail of `up` to it (ops.UpsampleLazyFn)
+        lazy = torch.is_grad_enabled() and x1.requires_grad and ops.upsample_lazy_plan(x1, size)
+        up, mru = (ops.UpsampleLazyFn if lazy else ops.UpsampleFn).apply(x1, size)
         x, mr = self.conv[0](x2, mr2, up, mru)
         for blk in list(self.conv)[1:]:
             x, mr = blk(x, mr)
