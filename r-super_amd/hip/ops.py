@@ -165,7 +165,7 @@ def rs_variant_epoch():
 def block_pack_specs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims=None, mixed=False):
     """The (up to) four fragment buffers a BasicBlock needs: forward conv1(+shortcut), forward conv2, data-gradient
     conv2, data-gradient conv1(+shortcut).  Returns (specs, bns) in that order.  mixed: one of the block's two sources is normalised, the other raw
-    (only conv1's forward launch reads them; every data gradient reads raw dY sources)."""
+    (conv1's forward launch reads them; every data gradient reads raw dY sources, and the one of conv1 then runs per source: the raw source takes no mask)."""
     Cout, Cin = w1.shape[0], Ca + Cb
     has_sc = ws is not None
     nc1 = Cout * (2 if has_sc else 1)
@@ -176,9 +176,12 @@ def block_pack_specs(w1, w2, ws, Ca, Cb, dtype, tiles_total, with_backward, dims
         bnd2, bnd1 = pick_bn(Cout, dtype, tiles_total, dims, epi=1), pick_bn(Cin, dtype, tiles_total, dims, epi=1)
         specs += [(1, w2, None, Cout, 0, Cout, 0, bnd2)]
         bns += [bnd2]
-        if split_dgrad_sources(Ca, Cb, dtype, tiles_total, bnd1):
-            # one data-gradient launch per forward source (column ranges [0, Ca) and [Ca, Ca + Cb) of the same GEMM): entries 3 and 4
-            bna, bnb = pick_bn(Ca, dtype, tiles_total, dims, epi=1), pick_bn(Cb, dtype, tiles_total, dims, epi=1)
+        if mixed or split_dgrad_sources(Ca, Cb, dtype, tiles_total, bnd1):
+            # one data-gradient launch per forward source (column ranges [0, Ca) and [Ca, Ca + Cb) of the same GEMM): entries 3 and 4.
+            # mixed: always -- the raw source has no ReLU mask and no InstanceNorm sums, its launch is a plain GEMM on the flipped weights (epi 0), so the
+            # widths are the ones every kernel takes in both directions (the plan of a mixed launch never answers with the depth-reuse kernel's own)
+            assert not mixed or Ca % 32 == 0, 'the data gradient of a block with one raw source runs per source: the first source needs a multiple of 32 channels'
+            bna, bnb = pick_bn(Ca, dtype, tiles_total, dims, epi=1, mixed=mixed), pick_bn(Cb, dtype, tiles_total, dims, epi=1, mixed=mixed)
             specs += [(1, w1, ws, Cout, Cout if has_sc else 0, Cin, Ca, bna), (1, w1, ws, Cout, Cout if has_sc else 0, Cin, (Ca << 16) | Cb, bnb)]
             bns += [bna, bnb]
         else:
@@ -672,10 +675,11 @@ class BasicBlockFn(torch.autograd.Function):
         y1 = Src(ys, C=Cout, mr=mr_y1)
         sdo = Src(dout)
         # conv2: data gradient (ReLU mask + IN sums fused), weight gradient
+        mixed = xb is not None and (mra is None) != (mrb is None)
         if ctx.packs is not None:
             bpk = (ctx.packs[0][2:], ctx.packs[1][2:])
         else:
-            bufs, bbns = block_packs(w1, w2, ws, Ca, Cb, dt, tiles * N, True, dims)
+            bufs, bbns = block_packs(w1, w2, ws, Ca, Cb, dt, tiles * N, True, dims, mixed)
             bpk = (bufs[2:], bbns[2:])
         bn, wpd2 = bpk[1][0], bpk[0][0]
         g1 = torch.empty((N, D, H, W, Cout), device=dev, dtype=dt)
@@ -695,6 +699,9 @@ class BasicBlockFn(torch.autograd.Function):
             g0s = [Src(torch.empty((N, D, H, W, Ca), device=dev, dtype=dt)), Src(torch.empty((N, D, H, W, Cb), device=dev, dtype=dt))]
             stats = []
             for g, src, wp_, bn in ((g0s[0], sa, bpk[0][1], bpk[1][1]), (g0s[1], sb, bpk[0][2], bpk[1][2])):
+                if src.mr is None:            # a raw source: no mask, no sums, no tail -- the transposed convolution is its gradient
+                    igemm(0, Src(dy1), sdo1, wp_, src.C, bn, dims, g.t)
+                    continue
                 part0 = part_buffer(dt, dims, src.C, bn, dev, epi=1)
                 igemm(1, Src(dy1), sdo1, wp_, src.C, bn, dims, g.t, part=part0, ea=src)
                 stats.append((part0, cnt, 1, 0))
@@ -717,16 +724,18 @@ class BasicBlockFn(torch.autograd.Function):
         lazy_a, lazy_b = ctx.needs_input_grad[1] and has_sc, xb is not None and ctx.needs_input_grad[3]
         if xb is None:
             gma, gmb = gm0[0], None
+        elif mixed:                                           # the one table of the normalised source
+            gma, gmb = (gm0[0], None) if mrb is None else (None, gm0[0])
         else:
             gma, gmb = gm0 if len(gm0) == 2 else gm0[0]       # one table per launch, or the joint launch's table split at Ca
 
         def raw(g):
             return g.t if g.C == g.ld else g.t[..., g.off:g.off + g.C]
-        if lazy_a:
+        if lazy_a or (mixed and mra is None):
             dxa = raw(g0s[0])
         else:
             dxa, gma = in_bwd_finalize(g0s[0], sa, gma, Ca, add1=None if has_sc else dout), None
-        if lazy_b:
+        if lazy_b or (mixed and mrb is None):
             dxb = raw(g0s[1])
         else:
             dxb, gmb = (None if xb is None else in_bwd_finalize(g0s[1], sb, gmb, Cb)), None
