@@ -242,8 +242,23 @@ int rsuper_pointwise_wgrad(int dtype, const float* dy, int ldy, const float* x, 
 int rsuper_stats_finalize(const float* part, int N, int nblk, int C, double cnt, float eps, int mode, int split, float* out, void* stream);
 /* The bandwidth-bound kernels around the convolutions (InstanceNorm backward tail, max pool, subsample, trilinear forward, plane partial sums):
  * 1 (default) = the tuned kernels and grids, 0 = the ones they replaced -- results are bit-identical, the switch serves A/B runs and tests
- * (RSUPER_GLUE_KERNELS=0 in the environment selects 0 at start-up).  Any other v queries.  Returns the value in effect. */
+ * (RSUPER_GLUE_KERNELS=0 in the environment selects 0 at start-up).  Any other v queries.  Returns the value in effect.  Which kernel and grid a
+ * launch of the family gets under either value is decided in one place (csrc/glue_plan.hpp) and can be asked with rsuper_glue_plan. */
 int rsuper_glue_variant(int v);
+/* Operations of that family, for the two queries below. */
+enum { RSUPER_GLUE_IN_BWD = 0, RSUPER_GLUE_POOL_FWD, RSUPER_GLUE_POOL_BWD, RSUPER_GLUE_SUB_FWD, RSUPER_GLUE_SUB_BWD, RSUPER_GLUE_UP_FWD,
+       RSUPER_GLUE_UP_BWD, RSUPER_GLUE_STEM_FWD };
+/* Rows of the partial statistics `part` ([N][rows][C][2]) that a forward writes for `vox` output voxels per sample -- the `blocks` argument of
+ * rsuper_maxpool2_fwd / rsuper_subsample2_fwd / rsuper_upsample_fwd, and the rows rsuper_stem_fwd writes.  0: the operation writes none. */
+int rsuper_stat_rows(int op, long vox);
+/* The launch the library makes for one operation, from the shape alone (pure host code; csrc/glue_plan.hpp is the one place that decides, and
+ * the entry points below read the same functions).  shape[7]: N, then vox (IN_BWD), the input's D, H, W (POOL_*, SUB_*) or ID, IH, IW, OD, OH, OW
+ * (UP_*); ld: the row stride that the kernels' 32-bit offsets see (the widest operand's; C for dense tensors).
+ * out[8]: kernel (0 in_bwd_finalize, 1 in_bwd_finalize2, 2 maxpool_fwd, 3 maxpool_fwd2, 4 maxpool_bwd, 5 subsample_fwd, 6 subsample_bwd,
+ * 7 upsample_fwd, 8 upsample_fwd2, 9 upsample_fwd3, 10 upsample_bwd, 11 upsample_bwd2, 12 upsample_bwd4), template selector (U of in_bwd_finalize2,
+ * NT of upsample_bwd4, else 0), blocks in x, y, z, threads per block, dynamic LDS bytes, rows of `part` (rsuper_stat_rows; 0: none).
+ * RSUPER_ERR_UNSUPPORTED where the launch would answer it, RSUPER_ERR_ARG for arguments that describe no launch. */
+int rsuper_glue_plan(int op, int dtype, const int* shape, int C, int ld, int* out);
 /* dx = rstd * (g - gm0 - x_n * gm1) [+ add1] [+ add2] */
 int rsuper_in_bwd_finalize(int dtype, const void* g, int ldg, const void* x, int ldx, const float* mr, const float* gm,
                            const void* add1, int lda1, const void* add2, int lda2, void* out, int ldo,

@@ -22,7 +22,8 @@ static inline bool pack_range_ok(int mode, int na, int nb) { return mode != 1 ||
 
 #include "igemm_plan.hpp"      // which kernel / block width / statistics rows a 3x3x3 igemm launch gets: igemm_plan, s2_kernel (needs dt_ok, bn_ok)
 #include "wgrad_plan.hpp"      // which kernel / configuration / split count a 3x3x3 weight-gradient launch gets: wgrad_plan (needs dt_ok)
-#include "lazy_tail_plan.hpp"  // which InstanceNorm backward tails run inside the kernel that consumes them: lazy_pool_plan (needs dt_ok)
+#include "glue_plan.hpp"       // which kernel / grid / LDS / statistics rows a launch of the bandwidth-bound glue kernels gets: glue_*_plan (needs dt_ok)
+#include "lazy_tail_plan.hpp"  // which InstanceNorm backward tails run inside the kernel that consumes them: lazy_pool_plan (needs dt_ok, glue_up_bwd_plan)
 
 // ---- optimiser: split the tensor list into kernel-argument sized chunks
 template <typename F>
@@ -402,20 +403,28 @@ int rsuper_stats_finalize(const float* part, int N, int nblk, int C, double cnt,
 }
 
 int rsuper_glue_variant(int v) { return rs_glue_variant(v); }
+int rsuper_stat_rows(int op, long vox) { return rs_stat_rows(op, vox); }
+int rsuper_glue_plan(int op, int dtype, const int* shape, int C, int ld, int* out) {
+    GluePlan pl;
+    if (!out) return RS_ERR_ARG;
+    if (const int rc = glue_plan_query(op, dtype, shape, C, ld, &pl)) return rc;
+    out[0] = pl.kernel; out[1] = pl.sel; out[2] = pl.bx; out[3] = pl.by; out[4] = pl.bz; out[5] = pl.threads; out[6] = pl.lds; out[7] = pl.rows;
+    return RS_OK;
+}
 
 int rsuper_in_bwd_finalize(int dtype, const void* g, int ldg, const void* x, int ldx, const float* mr, const float* gm,
                            const void* add1, int lda1, const void* add2, int lda2, void* out, int ldo,
                            int N, int vox, int C, void* stream) {
     if (!dt_ok(dtype) || !g || !x || !mr || !gm || !out || !ch_ok(C, ldg) || !ch_ok(C, ldx) || !ch_ok(C, ldo)) return RS_ERR_ARG;
     InBwdParams p = {g, ldg, x, ldx, mr, gm, add1, lda1, add2, lda2, out, ldo, N, vox, C};
-    return rs_launch_in_bwd(p, dtype, ST(stream));
+    return rs_launch_in_bwd(p, glue_in_bwd_plan(dtype, N, vox, C), ST(stream));
 }
 
 int rsuper_maxpool2_fwd(int dtype, const void* x, int ldx, void* y, int ldy, float* part, int blocks,
                         int N, int D, int H, int W, int C, void* stream) {
     if (!dt_ok(dtype) || !x || !y || !ch_ok(C, ldx) || !ch_ok(C, ldy) || blocks <= 0 || D < 2 || H < 2 || W < 2) return RS_ERR_ARG;
     PoolParams p = {x, ldx, y, ldy, nullptr, 0, part, N, D, H, W, C};
-    return rs_launch_pool(p, dtype, 0, blocks, ST(stream));
+    return rs_launch_pool(p, glue_pool_fwd_plan(dtype, N, C, blocks), ST(stream));
 }
 int rsuper_maxpool2_bwd(int dtype, const void* x, int ldx, const void* dy, int lddy, void* dx, int lddx,
                         int N, int D, int H, int W, int C, void* stream) {
@@ -426,14 +435,14 @@ int rsuper_maxpool2_bwd(int dtype, const void* x, int ldx, const void* dy, int l
         if (const int rc = rs_launch_zero_bytes(dx, (size_t)N * D * H * W * C * (dtype == RS_F32 ? 4 : 2), ST(stream))) return rc;   // a kernel, not a memset node
     }
     PoolParams p = {x, ldx, (void*)dy, lddy, dx, lddx, nullptr, N, D, H, W, C};
-    return rs_launch_pool(p, dtype, 1, 1, ST(stream));
+    return rs_launch_pool(p, glue_pool_bwd_plan(dtype, N, D, H, W, C), ST(stream));
 }
 int rsuper_maxpool2_bwd_add(int dtype, const void* x, int ldx, const void* dy, int lddy, const void* add, int lda, void* dx, int lddx,
                             int N, int D, int H, int W, int C, void* stream) {
     if (!dt_ok(dtype) || !x || !dy || !add || !dx || !ch_ok(C, ldx) || !ch_ok(C, lddy) || !ch_ok(C, lda) || !ch_ok(C, lddx)) return RS_ERR_ARG;
     if ((D & 1) || (H & 1) || (W & 1)) return RS_ERR_UNSUPPORTED;   // the never-pooled trailing planes would need a copy of `add`: the caller adds the two gradients itself
     PoolParams p = {x, ldx, (void*)dy, lddy, dx, lddx, nullptr, N, D, H, W, C, add, lda};
-    return rs_launch_pool(p, dtype, 1, 1, ST(stream));
+    return rs_launch_pool(p, glue_pool_bwd_plan(dtype, N, D, H, W, C), ST(stream));
 }
 int rsuper_lazy_tails(int v) { return lazy_tails_variant(v); }
 int rsuper_maxpool2_bwd_lazy_plan(int dtype, int N, int D, int H, int W, int C) { return lazy_pool_plan(dtype, N, D, H, W, C); }
@@ -445,32 +454,32 @@ int rsuper_maxpool2_bwd_lazy(int dtype, const void* x, int ldx, const void* dy, 
         return RS_ERR_ARG;
     if (lazy_pool_plan(dtype, N, D, H, W, C) != 1) return RS_ERR_UNSUPPORTED;      // the caller finalises the gradients and takes rsuper_maxpool2_bwd_add's path
     PoolParams p = {x, ldx, (void*)dy, lddy, dx, lddx, nullptr, N, D, H, W, C, add, lda, gm_y ? mr_y : nullptr, gm_y, gm_x ? mr_x : nullptr, gm_x};
-    return rs_launch_pool(p, dtype, 1, 1, ST(stream));
+    return rs_launch_pool(p, glue_pool_bwd_plan(dtype, N, D, H, W, C), ST(stream));
 }
 
 int rsuper_subsample2_fwd(int dtype, const void* x, int ldx, void* y, int ldy, float* part, int blocks,
                           int N, int D, int H, int W, int C, void* stream) {
     if (!dt_ok(dtype) || !x || !y || !ch_ok(C, ldx) || !ch_ok(C, ldy) || blocks <= 0 || D < 1 || H < 1 || W < 1 || N <= 0) return RS_ERR_ARG;
     PoolParams p = {x, ldx, y, ldy, nullptr, 0, part, N, D, H, W, C};
-    return rs_launch_subsample(p, dtype, 0, blocks, ST(stream));
+    return rs_launch_subsample(p, glue_sub_fwd_plan(dtype, N, C, blocks), ST(stream));
 }
 int rsuper_subsample2_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx, int N, int D, int H, int W, int C, void* stream) {
     if (!dt_ok(dtype) || !dy || !dx || !ch_ok(C, lddy) || !ch_ok(C, lddx) || D < 1 || H < 1 || W < 1 || N <= 0) return RS_ERR_ARG;
     PoolParams p = {nullptr, 0, (void*)dy, lddy, dx, lddx, nullptr, N, D, H, W, C};
-    return rs_launch_subsample(p, dtype, 1, 1, ST(stream));
+    return rs_launch_subsample(p, glue_sub_bwd_plan(dtype, N, D, H, W, C), ST(stream));
 }
 
 int rsuper_upsample_fwd(int dtype, const void* x, int ldx, void* y, int ldy, float* part, int blocks,
                         int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, void* stream) {
     if (!dt_ok(dtype) || !x || !y || !ch_ok(C, ldx) || !ch_ok(C, ldy) || blocks <= 0) return RS_ERR_ARG;
     UpParams p = {x, ldx, y, ldy, nullptr, 0, part, N, ID, IH, IW, OD, OH, OW, C};
-    return rs_launch_upsample(p, dtype, 0, blocks, ST(stream));
+    return rs_launch_upsample(p, glue_up_fwd_plan(dtype, N, ID, IH, IW, OD, OH, OW, C, ldx, blocks), ST(stream));
 }
 int rsuper_upsample_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx,
                         int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, void* stream) {
     if (!dt_ok(dtype) || !dy || !dx || !ch_ok(C, lddy) || !ch_ok(C, lddx)) return RS_ERR_ARG;
     UpParams p = {nullptr, 0, (void*)dy, lddy, dx, lddx, nullptr, N, ID, IH, IW, OD, OH, OW, C};
-    return rs_launch_upsample(p, dtype, 1, 1, ST(stream));
+    return rs_launch_upsample(p, glue_up_bwd_plan(dtype, N, ID, IH, IW, OD, OH, OW, C, lddy), ST(stream));
 }
 int rsuper_upsample_bwd_lazy_plan(int dtype, int N, int ID, int IH, int IW, int OD, int OH, int OW, int C) {
     return lazy_up_plan(dtype, N, ID, IH, IW, OD, OH, OW, C);
@@ -481,7 +490,10 @@ int rsuper_upsample_bwd_lazy(int dtype, const void* g, int ldg, const void* u, i
     const int pl = lazy_up_plan(dtype, N, ID, IH, IW, OD, OH, OW, C);
     if (pl < 0) return RS_ERR_ARG;
     if (pl != 1) return RS_ERR_UNSUPPORTED;                      // the caller finalises g and calls rsuper_upsample_bwd
-    return rs_launch_upsample_bwd_lazy(g, ldg, u, ldu, mr, gm, dx, lddx, N, ID, IH, IW, OD, OH, OW, C, ST(stream));
+    const GluePlan gp = glue_up_bwd_plan(dtype, N, ID, IH, IW, OD, OH, OW, C, ldg > ldu ? ldg : ldu);
+    if (gp.kernel != GLUE_UP_BWD4) return RS_ERR_UNSUPPORTED;    // row strides beyond the kernel's 32-bit offsets
+    UpParams p = {nullptr, 0, (void*)g, ldg, dx, lddx, nullptr, N, ID, IH, IW, OD, OH, OW, C};
+    return rs_launch_upsample(p, gp, ST(stream), u, ldu, mr, gm);
 }
 int rsuper_stem_fwd(int dtype, const float* x, const float* w, void* y, int ldy, float* part,
                     int N, int D, int H, int W, int C, void* stream) {

@@ -3,7 +3,7 @@
 // gradient g with the statistics and apply the tail as it reads ("lazy" gradient).  Nothing here launches anything and nothing elsewhere decides:
 // api.hip's queries (rsuper_maxpool2_bwd_lazy_plan / rsuper_upsample_bwd_lazy_plan, which the modules ask before they hand out a differentiable
 // statistics tensor) and its launches (rsuper_maxpool2_bwd_lazy / rsuper_upsample_bwd_lazy) read lazy_pool_plan / lazy_up_plan.  Included by api.hip
-// only (after its dt_ok helper); tests/test_lazy_tail_plan_cpu.py pins the answers.
+// only (after its dt_ok helper and glue_plan.hpp); tests/test_lazy_tail_plan_cpu.py pins the answers.
 #pragma once
 #include <stdlib.h>
 #include "common.hpp"
@@ -40,10 +40,12 @@ static int lazy_pool_plan(int dtype, int N, int D, int H, int W, int C) {
 //     12^3 -> 24^3 x 256     9.9 + 17.0 us    29.5 us      ( 8.7 + 12.6 against 26.2 us)
 //      6^3 -> 12^3 x 320    ~5.2 + 16.1 us    27.8 us      ( 8.4 + 11.8 against 22.3 us)
 // No gain at 96^3 and a loss at the three smaller shapes, and nothing suggests a shape in between where it would win: the default keeps two launches
-// everywhere.  The fused kernel stays selectable (rsuper_lazy_tails(2)) for tests and for measuring a changed kernel.  Scales whose tile tables the kernel
-// does not hold are refused by the launch itself (RS_ERR_UNSUPPORTED).
+// everywhere.  The fused kernel stays selectable (rsuper_lazy_tails(2)) for tests and for measuring a changed kernel, and only where the trilinear
+// backward's own plan (glue_plan.hpp) names the row-sharing kernel: a scale its tile tables do not hold, or RSUPER_UPSAMPLE_BWD4=0, answers 0 here, so
+// no module hands out a differentiable statistics tensor for a launch that will not happen.  Asked for dense tensors (row stride C); the launch
+// asks again with the strides it got.
 static int lazy_up_plan(int dtype, int N, int ID, int IH, int IW, int OD, int OH, int OW, int C) {
     if (!dt_ok(dtype) || N <= 0 || ID <= 0 || IH <= 0 || IW <= 0 || OD <= 0 || OH <= 0 || OW <= 0 || C <= 0) return -1;
-    if (dtype != RS_BF16 || (C % 8) || N > 65535) return 0;
-    return lazy_tails_variant(-1) == 2;
+    if (dtype != RS_BF16 || (C % 8) || N > 65535 || lazy_tails_variant(-1) != 2) return 0;
+    return glue_up_bwd_plan(dtype, N, ID, IH, IW, OD, OH, OW, C, C).kernel == GLUE_UP_BWD4;
 }

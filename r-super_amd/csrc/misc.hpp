@@ -75,12 +75,31 @@ int rs_launch_depthwise(const float* x, const float* w, float* y, int N, int D, 
 int rs_launch_depthwise_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int D, int H, int W, int C, hipStream_t st);
 int rs_launch_stats_finalize(const float* part, int N, int nblk, int C, double cnt, float eps, int mode, int split, float* out, hipStream_t st);
 int rs_elem_blocks(size_t items);
-int rs_glue_variant(int v);      // 1: tuned bandwidth-bound kernels (default), 0: the ones they replaced; other values query
-int rs_launch_in_bwd(const InBwdParams& p, int dtype, hipStream_t st);
-int rs_launch_pool(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st);
-int rs_launch_subsample(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st);
-int rs_launch_upsample(const UpParams& p, int dtype, int bwd, int blocks, hipStream_t st);
-int rs_launch_upsample_bwd_lazy(const void* g, int ldg, const void* u, int ldu, const float* mr, const float* gm, void* dx, int lddx,
-                                int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, hipStream_t st);      // bf16 only
+int rs_glue_variant(int v);      // 1: tuned bandwidth-bound kernels (default), 0: the ones they replaced; other values query (defined in glue_plan.hpp)
+
+// One launch of the bandwidth-bound "glue" family of unet_misc.hip, as glue_plan.hpp decides it and the launchers below carry it out: the launchers
+// switch over `kernel` and look at no shape, limit or environment variable themselves.  rsuper_glue_plan hands the same fields to tests.
+enum GlueOp { GLUE_OP_IN_BWD, GLUE_OP_POOL_FWD, GLUE_OP_POOL_BWD, GLUE_OP_SUB_FWD, GLUE_OP_SUB_BWD, GLUE_OP_UP_FWD, GLUE_OP_UP_BWD, GLUE_OP_STEM_FWD };
+enum GlueKernel {                // one value per __global__ of the family; GLUE_NONE: the launch answers RS_ERR_UNSUPPORTED
+    GLUE_NONE = -1, GLUE_IN_BWD, GLUE_IN_BWD2, GLUE_POOL_FWD, GLUE_POOL_FWD2, GLUE_POOL_BWD, GLUE_SUB_FWD, GLUE_SUB_BWD,
+    GLUE_UP_FWD, GLUE_UP_FWD2, GLUE_UP_FWD3, GLUE_UP_BWD, GLUE_UP_BWD2, GLUE_UP_BWD4
+};
+struct GluePlan {
+    int kernel;                  // GlueKernel
+    int sel;                     // template selector: U of in_bwd_finalize2 (2, 4), NT of upsample_bwd4 (4, 6); 0 elsewhere
+    int bx, by, bz, threads;     // grid and workgroup
+    int lds;                     // dynamic LDS bytes
+    int rows;                    // rows of `part` the kernel writes per sample (= bx), 0: none
+    int dtype;
+    int arg;                     // the kernel argument that goes with the grid: cv_shift of in_bwd_finalize2, nbx of upsample_bwd4
+};
+int rs_stat_rows(int op, long vox);      // rows of `part` of a statistics-row forward (GlueOp; vox: output voxels per sample), 0: the op writes none
+int rs_launch_in_bwd(const InBwdParams& p, const GluePlan& pl, hipStream_t st);
+int rs_launch_pool(const PoolParams& p, const GluePlan& pl, hipStream_t st);
+int rs_launch_subsample(const PoolParams& p, const GluePlan& pl, hipStream_t st);
+// forward and the gather backward kernels; GLUE_UP_BWD4 with u, mr, gm (or nullptr): the lazy operands -- p.y is then a raw data gradient and the
+// kernel applies its InstanceNorm backward tail (u the up-sampled tensor, row stride ldu; mr, gm [N][C][2])
+int rs_launch_upsample(const UpParams& p, const GluePlan& pl, hipStream_t st, const void* u = nullptr, int ldu = 0, const float* mr = nullptr,
+                       const float* gm = nullptr);
 int rs_launch_stem(const StemParams& p, int dtype, int wgrad, hipStream_t st);
 int rs_launch_head(const HeadParams& p, int dtype, int which, hipStream_t st);

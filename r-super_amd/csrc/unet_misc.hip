@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "misc.hpp"
+#include "up_coord.hpp"      // lin_coord, up_range, up_weight and the table entries: shared with the host-only dispatch (glue_plan.hpp)
 
 namespace {
 
@@ -442,17 +443,6 @@ __global__ void subsample_bwd_kernel(PoolParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------ trilinear, align_corners
-__host__ __device__ __forceinline__ void lin_coord(int o, float scale, int I, int& i0, int& i1, float& l1) {
-    // ATen area_pixel_compute_source_index(align_corners=True): src = scale * dst (float32).  No contraction of `scale * o - i0` into one fma: the
-    // host sizes the backward kernel's tap tables with this same function and must see the same zero / non-zero weights as the device
-#pragma clang fp contract(off)
-    const float src = scale * (float)o;
-    i0 = (int)src;
-    if (i0 > I - 1) i0 = I - 1;
-    i1 = i0 + (i0 < I - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
-
 template <typename T>
 __global__ void upsample_fwd_kernel(UpParams p) {
     constexpr int KP = Elem<T>::KP;
@@ -514,23 +504,6 @@ __global__ void upsample_fwd_kernel(UpParams p) {
             }
         }
     if (p.part) block_channel_sums<KP>(s1, s2, p.C, CV, VL, vl, s, active, p.part + ((size_t)n * gridDim.x + blockIdx.x) * p.C * 2);
-}
-
-// contribution range of input index i along one axis: outputs o whose i0(o)==i or i1(o)==i
-__host__ __device__ __forceinline__ void up_range(int i, float scale, int O, int& lo, int& hi) {
-    if (scale <= 0.f) { lo = 0; hi = O - 1; return; }
-    lo = (int)floorf((float)(i - 1) / scale) - 1;
-    hi = (int)ceilf((float)(i + 1) / scale) + 1;
-    if (lo < 0) lo = 0;
-    if (hi > O - 1) hi = O - 1;
-}
-__host__ __device__ __forceinline__ float up_weight(int o, int i, float scale, int I) {
-    int i0, i1; float l1;
-    lin_coord(o, scale, I, i0, i1, l1);
-    float w = 0.f;
-    if (i0 == i) w += 1.f - l1;
-    if (i1 == i) w += l1;
-    return w;
 }
 
 // per-axis candidate outputs of one input index and their interpolation weights (at most 6 for any scale >= 1/4)
@@ -678,7 +651,6 @@ __global__ __launch_bounds__(256) void upsample_fwd2_kernel(UpParams p) {
 // maxpool_fwd2_kernel): y and `part` are bit-identical.  Measured 99.6 -> 92 us at 96^3 x 64 (profiles/glue_kernels_ab.md): issue was not the only
 // bound.  A second register set that keeps the next output's eight loads in flight during the accumulation measured the same (93 us) and was not
 // kept; what remains is 8 KB of L1 requests per KB written, which only sharing corners between neighbouring outputs (another voxel walk) removes.
-struct UpTab { uint32_t o0, o1; float l0, l1; };
 template <typename T>
 __global__ __launch_bounds__(256) void upsample_fwd3_kernel(UpParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -777,8 +749,6 @@ __global__ __launch_bounds__(256) void upsample_fwd3_kernel(UpParams p) {
 // taps in the same ascending (a, b, c) order as upsample_bwd_kernel (zero-weight candidates it skipped contributed
 // nothing), so results are bit-identical; the innermost loop is unrolled to the block's maximal W count and its loads go
 // through a buffer descriptor (out-of-range -> zeros, no branch), so NW loads are in flight per (a, b).
-constexpr int UP_MAXW = 12;      // contributing outputs per input index: <= 2 / scale + 2, i.e. up to 4x up-sampling (the aux head)
-struct UpEnt { int lo, n; float w[UP_MAXW]; };
 template <typename T, int NW>
 __device__ __forceinline__ void up_bwd_rows(const UpParams& p, const UpEnt* td, const UpEnt* th, const UpEnt* tw, int n, uint32_t i0, uint32_t total,
                                             uint32_t stride) {
@@ -896,7 +866,6 @@ struct UpInParams {
 #ifndef UP4_SL
 #define UP4_SL 2
 #endif
-constexpr int UP4_ROWS = 16;       // candidate output rows of a pair of input indices (up_range of the first .. of the second): <= 2 * 2 / scale + 6
 // LAZY: every loaded vector of g gets the tail of in_bwd_finalize (with the vector of u at the same voxel) and the rounding of the tensor that launch
 // would have written; weights and accumulation order are untouched, so dx is bit for bit that of in_bwd_finalize + this kernel.  The second operand
 // buffers and the 32 per-channel constants do not fit three blocks per CU: the lazy instantiations run two.
@@ -1058,31 +1027,6 @@ __global__ __launch_bounds__(256, LAZY ? 2 : 3) void upsample_bwd4_kernel(UpInPa
         if (id < p.ID && ih < p.IH)
             *(uint4*)((T*)p.dx + ((size_t)((n * p.ID + id) * p.IH + ih) * p.IW + iw) * p.lddx + s * CPT) = pack16<T>(acc[i]);
     }
-}
-// largest number of contributing outputs of any input index of one axis (the arithmetic of the kernel: lin_coord is not contracted on either side)
-static int up_max_count(int I, int O) {
-    const float sc = O > 1 ? (float)(I - 1) / (float)(O - 1) : 0.f;
-    int m = 1;
-    for (int i = 0; i < I; ++i) {
-        int lo, hi;
-        up_range(i, sc, O, lo, hi);
-        int first = -1, last = -2;
-        for (int o = lo; o <= hi; ++o)
-            if (up_weight(o, i, sc, I) != 0.f) { if (first < 0) first = o; last = o; }
-        if (last - first + 1 > m) m = last - first + 1;
-    }
-    return m;
-}
-static int up_pair_window(int I, int O) {                        // widest candidate window (up_range) of an aligned pair of input indices
-    const float sc = O > 1 ? (float)(I - 1) / (float)(O - 1) : 0.f;
-    int m = 1;
-    for (int i = 0; i < I; i += 2) {
-        int lo, hi, lo2, hi2;
-        up_range(i, sc, O, lo, hi);
-        if (i + 1 < I) { up_range(i + 1, sc, O, lo2, hi2); if (hi2 > hi) hi = hi2; }
-        if (hi - lo + 1 > m) m = hi - lo + 1;
-    }
-    return m;
 }
 
 // ------------------------------------------------------------------------------------------------ stem: Conv3d(1 -> C, 3x3x3)
@@ -1523,197 +1467,76 @@ int rs_elem_blocks(size_t items) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-// 1 (default): the tuned bandwidth-bound kernels of this file and of loss.hip (in_bwd_finalize2, maxpool_fwd2, upsample_fwd3, channel-split grids,
-// pipelined plane_partials_fwd); 0: the kernels and grids they replaced (A/B runs and tests/test_gpu_glue_kernels.py: results are bit-identical).
-// RSUPER_GLUE_KERNELS=0 in the environment selects 0 at start-up.
-int rs_glue_variant(int v) {
-    static int g = !(getenv("RSUPER_GLUE_KERNELS") && atoi(getenv("RSUPER_GLUE_KERNELS")) == 0);
-    if (v == 0 || v == 1) g = v;
-    return g;
-}
+// The glue launchers carry out a GluePlan (misc.hpp): which kernel, grid, workgroup and LDS is glue_plan.hpp's decision, made in api.hip.  What is
+// left here is the switch over plan.kernel and, for the lazy instantiations, which operand pointers are set.
+// RS_GLUE_LAUNCH: the f32 or bf16 instantiation of a kernel written in terms of T, on the plan's grid.
+#define RS_GLUE_LAUNCH(KERNEL_OF_T, ...)                                                                                                              \
+    if (pl.dtype == RS_F32) { using T = float; hipLaunchKernelGGL(KERNEL_OF_T, dim3(pl.bx, pl.by, pl.bz), dim3(pl.threads), pl.lds, st, __VA_ARGS__); } \
+    else { using T = bf16_t; hipLaunchKernelGGL(KERNEL_OF_T, dim3(pl.bx, pl.by, pl.bz), dim3(pl.threads), pl.lds, st, __VA_ARGS__); }
 
-// Channel split of the kernels that write statistics rows (max pool, subsample, trilinear forward): `rows` is the row count of `part` and their
-// gridDim.x.  Where rows * N leaves most of the chip idle, z blocks of CV / z channel vectors (at least 128 bytes of a voxel, at least one wave)
-// share a row.
-static int stat_csplit(int rows, int N, int CV) {
-    if (!rs_glue_variant(-1)) return 1;
-    const int VL = 256 / CV;
-    int z = 1;
-    while ((size_t)rows * N * z < 1024 && CV % (2 * z) == 0 && CV / (2 * z) >= 8 && (CV / (2 * z)) * VL >= 64) z *= 2;
-    return z;
-}
-
-int rs_launch_in_bwd(const InBwdParams& p, int dtype, hipStream_t st) {
-    const int KP = dtype == RS_F32 ? 4 : 8;
-    if ((size_t)p.vox * (p.C / KP) >= 0xFFFFFFFFull) return RS_ERR_UNSUPPORTED;
-    const int blocks = rs_elem_blocks((size_t)p.vox * (p.C / KP));
-    // one or two vectors per thread on the grid below (up to 48^3 x 128 channels at bf16): several vectors per thread, all loads up front.  Larger
-    // tensors loop on 4096 blocks and run at the HBM rate already
-    const uint32_t CV = (uint32_t)(p.C / KP);
-    const size_t nb1 = ((size_t)p.vox * CV + 255) / 256;
-    if (rs_glue_variant(-1) && CV > 0 && (CV & (CV - 1)) == 0 && CV <= 256 && nb1 >= 256 && nb1 <= 8192) {
-        const int sh = __builtin_ctz(CV);
-        if (nb1 >= 1024) {
-            const dim3 grid((unsigned)((nb1 + 3) / 4), p.N);
-            if (dtype == RS_F32) hipLaunchKernelGGL((in_bwd_finalize2_kernel<float, 4>), grid, dim3(256), 0, st, p, sh);
-            else hipLaunchKernelGGL((in_bwd_finalize2_kernel<bf16_t, 4>), grid, dim3(256), 0, st, p, sh);
-        } else {
-            const dim3 grid((unsigned)((nb1 + 1) / 2), p.N);
-            if (dtype == RS_F32) hipLaunchKernelGGL((in_bwd_finalize2_kernel<float, 2>), grid, dim3(256), 0, st, p, sh);
-            else hipLaunchKernelGGL((in_bwd_finalize2_kernel<bf16_t, 2>), grid, dim3(256), 0, st, p, sh);
-        }
-        return rs_check_launch();
-    }
-    if (dtype == RS_F32) hipLaunchKernelGGL(in_bwd_finalize_kernel<float>, dim3(blocks, p.N), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(in_bwd_finalize_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), 0, st, p);
-    return rs_check_launch();
-}
-
-int rs_launch_pool(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st) {
-    const int KP = dtype == RS_F32 ? 4 : 8;
-    const int CV = p.C / KP;
-    if (CV > 256) return RS_ERR_UNSUPPORTED;
-    if (!bwd) {
-        const size_t smem = (size_t)(256 / CV) * p.C * 2 * sizeof(float);
-        if (rs_glue_variant(-1) && (size_t)blocks * p.N < 1024) {                  // small volumes: channel-split grid, four voxels of loads in flight
-            const int z = stat_csplit(blocks, p.N, CV);
-            const dim3 grid(blocks, p.N, z), blk(z == 1 ? 256 : (CV / z) * (256 / CV));
-            if (dtype == RS_F32) hipLaunchKernelGGL((maxpool_fwd2_kernel<float, 4>), grid, blk, smem / z, st, p);
-            else hipLaunchKernelGGL((maxpool_fwd2_kernel<bf16_t, 4>), grid, blk, smem / z, st, p);
-        } else {
-            if (dtype == RS_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
-            else hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);
-        }
-    } else {
-        const size_t items = (size_t)(p.D / 2) * (p.H / 2) * (p.W / 2) * CV;
-        int b = rs_elem_blocks(items), threads = 256;
-        if (rs_glue_variant(-1) && (size_t)b * p.N < 512) { threads = 64; b = (int)((items + 63) / 64); }      // small volumes: one wave per block, four times the CUs
-        const int lazy = (p.gm_y ? 1 : 0) | (p.gm_x ? 2 : 0);
-        if ((p.gm_y && !p.mr_y) || (p.gm_x && (!p.mr_x || !p.add))) return RS_ERR_ARG;
-#define RS_POOL_BWD(LZ)                                                                                                   \
-        case LZ:                                                                                                          \
-            if (dtype == RS_F32) hipLaunchKernelGGL((maxpool_bwd_kernel<float, LZ>), dim3(b, p.N), dim3(threads), 0, st, p);   \
-            else hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, LZ>), dim3(b, p.N), dim3(threads), 0, st, p);             \
+int rs_launch_in_bwd(const InBwdParams& p, const GluePlan& pl, hipStream_t st) {
+    switch (pl.kernel) {
+        case GLUE_IN_BWD: RS_GLUE_LAUNCH(in_bwd_finalize_kernel<T>, p) break;
+        case GLUE_IN_BWD2:
+            if (pl.sel == 4) { RS_GLUE_LAUNCH((in_bwd_finalize2_kernel<T, 4>), p, pl.arg) }
+            else { RS_GLUE_LAUNCH((in_bwd_finalize2_kernel<T, 2>), p, pl.arg) }
             break;
-        switch (lazy) { RS_POOL_BWD(0) RS_POOL_BWD(1) RS_POOL_BWD(2) RS_POOL_BWD(3) }
-#undef RS_POOL_BWD
+        default: return RS_ERR_UNSUPPORTED;
     }
     return rs_check_launch();
 }
 
-int rs_launch_subsample(const PoolParams& p, int dtype, int bwd, int blocks, hipStream_t st) {
-    const int KP = dtype == RS_F32 ? 4 : 8;
-    const int CV = p.C / KP;
-    if (CV > 256) return RS_ERR_UNSUPPORTED;
-    if (!bwd) {
-        const size_t smem = (size_t)(256 / CV) * p.C * 2 * sizeof(float);
-        const int z = stat_csplit(blocks, p.N, CV);
-        const dim3 grid(blocks, p.N, z), blk(z == 1 ? 256 : (CV / z) * (256 / CV));
-        if (dtype == RS_F32) hipLaunchKernelGGL(subsample_fwd_kernel<float>, grid, blk, smem / z, st, p);
-        else hipLaunchKernelGGL(subsample_fwd_kernel<bf16_t>, grid, blk, smem / z, st, p);
-    } else {
-        const int b = rs_elem_blocks((size_t)p.D * p.H * p.W * CV);
-        if (dtype == RS_F32) hipLaunchKernelGGL(subsample_bwd_kernel<float>, dim3(b, p.N), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(subsample_bwd_kernel<bf16_t>, dim3(b, p.N), dim3(256), 0, st, p);
+int rs_launch_pool(const PoolParams& p, const GluePlan& pl, hipStream_t st) {
+    switch (pl.kernel) {
+        case GLUE_POOL_FWD: RS_GLUE_LAUNCH(maxpool_fwd_kernel<T>, p) break;
+        case GLUE_POOL_FWD2: RS_GLUE_LAUNCH((maxpool_fwd2_kernel<T, 4>), p) break;
+        case GLUE_POOL_BWD:
+            if ((p.gm_y && !p.mr_y) || (p.gm_x && (!p.mr_x || !p.add))) return RS_ERR_ARG;
+            switch ((p.gm_y ? 1 : 0) | (p.gm_x ? 2 : 0)) {       // which gradients are lazy
+                case 0: RS_GLUE_LAUNCH((maxpool_bwd_kernel<T, 0>), p) break;
+                case 1: RS_GLUE_LAUNCH((maxpool_bwd_kernel<T, 1>), p) break;
+                case 2: RS_GLUE_LAUNCH((maxpool_bwd_kernel<T, 2>), p) break;
+                case 3: RS_GLUE_LAUNCH((maxpool_bwd_kernel<T, 3>), p) break;
+            }
+            break;
+        default: return RS_ERR_UNSUPPORTED;
     }
     return rs_check_launch();
 }
 
-// trilinear backward on the row-sharing kernel (bf16); RS_ERR_UNSUPPORTED for scales its tile tables do not hold (the caller runs upsample_bwd2 then)
-// lz (or nullptr): the lazy operands (u, ldu, mr, gm of UpInParams) -- g is then a raw data gradient and the kernel applies its InstanceNorm backward tail
-static int launch_upsample_bwd4(const void* g, int ldg, void* dx, int lddx, int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, hipStream_t st,
-                                const UpInParams* lz = nullptr) {
-    static const bool off = getenv("RSUPER_UPSAMPLE_BWD4") && atoi(getenv("RSUPER_UPSAMPLE_BWD4")) == 0;
-    if (off || (C % 8) || N > 65535) return RS_ERR_UNSUPPORTED;
-    if ((size_t)OD * OH * OW * (size_t)ldg * 2 >= 0xFFFFFFFFull) return RS_ERR_UNSUPPORTED;                    // 32-bit byte offsets
-    if (lz && (size_t)OD * OH * OW * (size_t)lz->ldu * 2 >= 0xFFFFFFFFull) return RS_ERR_UNSUPPORTED;
-    // the table sizes depend on the shape only: remembered per (ID, IH, IW, OD, OH, OW) (the host loops cost a few microseconds per call otherwise)
-    struct Memo { int k[6]; int ok, nmax; };
-    static thread_local Memo memo[8] = {};
-    static thread_local int memo_next = 0;
-    const int key[6] = {ID, IH, IW, OD, OH, OW};
-    const Memo* hit = nullptr;
-    for (int i = 0; i < 8 && !hit; ++i) if (memo[i].k[0] && !memcmp(memo[i].k, key, sizeof(key))) hit = &memo[i];
-    if (!hit) {
-        Memo& m = memo[memo_next++ & 7];
-        memcpy(m.k, key, sizeof(key));
-        m.ok = up_pair_window(ID, OD) <= UP4_ROWS && up_pair_window(IH, OH) <= UP4_ROWS;
-        m.nmax = up_max_count(IW, OW);
-        hit = &m;
-    }
-    if (!hit->ok) return RS_ERR_UNSUPPORTED;
-    const int nmax = hit->nmax;
-    if (nmax > 6) return RS_ERR_UNSUPPORTED;
-    UpInParams p = {g, ldg, dx, lddx, N, ID, IH, IW, OD, OH, OW, C};
-    if (lz) { p.u = lz->u; p.ldu = lz->ldu; p.mr = lz->mr; p.gm = lz->gm; }
-    const int nbx = (IW * (C / 8) + 255) / 256;
-    const unsigned blocks = (unsigned)(((ID + 1) / 2) * ((IH + 1) / 2) * nbx);
-    if (lz) {
-        if (nmax <= 4) hipLaunchKernelGGL((upsample_bwd4_kernel<4, true>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
-        else hipLaunchKernelGGL((upsample_bwd4_kernel<6, true>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
-    } else {
-        if (nmax <= 4) hipLaunchKernelGGL((upsample_bwd4_kernel<4, false>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
-        else hipLaunchKernelGGL((upsample_bwd4_kernel<6, false>), dim3(blocks, N), dim3(256), 0, st, p, nbx);
+int rs_launch_subsample(const PoolParams& p, const GluePlan& pl, hipStream_t st) {
+    switch (pl.kernel) {
+        case GLUE_SUB_FWD: RS_GLUE_LAUNCH(subsample_fwd_kernel<T>, p) break;
+        case GLUE_SUB_BWD: RS_GLUE_LAUNCH(subsample_bwd_kernel<T>, p) break;
+        default: return RS_ERR_UNSUPPORTED;
     }
     return rs_check_launch();
 }
 
-// trilinear backward of a lazy gradient: the row-sharing kernel or RS_ERR_UNSUPPORTED (the caller finalises g and calls rs_launch_upsample)
-int rs_launch_upsample_bwd_lazy(const void* g, int ldg, const void* u, int ldu, const float* mr, const float* gm, void* dx, int lddx,
-                                int N, int ID, int IH, int IW, int OD, int OH, int OW, int C, hipStream_t st) {
-    static const bool v1 = getenv("RSUPER_UPSAMPLE_V1") != nullptr;
-    if (v1) return RS_ERR_UNSUPPORTED;
-    UpInParams lz = {};
-    lz.u = u; lz.ldu = ldu; lz.mr = mr; lz.gm = gm;
-    return launch_upsample_bwd4(g, ldg, dx, lddx, N, ID, IH, IW, OD, OH, OW, C, st, &lz);
-}
-
-int rs_launch_upsample(const UpParams& p, int dtype, int bwd, int blocks, hipStream_t st) {
-    const int KP = dtype == RS_F32 ? 4 : 8;
-    const int CV = p.C / KP;
-    if (CV > 256) return RS_ERR_UNSUPPORTED;
-    if (!bwd) {
-        static const bool v1 = getenv("RSUPER_UPSAMPLE_V1") != nullptr;      // first-generation kernels (A/B, bit-identical results)
-        const size_t smem = (size_t)(256 / CV) * p.C * 2 * sizeof(float);
-        const bool small = (size_t)p.N * p.ID * p.IH * p.IW * p.ldx < 0x7FFFFFFFull;
-        const size_t tab3 = (size_t)(p.OD + p.OH + p.OW) * sizeof(UpTab);
-        const bool fwd3 = rs_glue_variant(-1) && small && (size_t)p.ID * p.IH * p.IW * p.ldx * (dtype == RS_F32 ? 4 : 2) < 0xFFFFFFFFull && smem + tab3 <= 64 * 1024;
-        if (v1 || !small) {
-            if (dtype == RS_F32) hipLaunchKernelGGL(upsample_fwd_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
-            else hipLaunchKernelGGL(upsample_fwd_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);
-        } else if (fwd3) {                                       // table-driven kernel, channel-split grid on small volumes
-            const int z = stat_csplit(blocks, p.N, CV);
-            const dim3 grid(blocks, p.N, z), blk(z == 1 ? 256 : (CV / z) * (256 / CV));
-            if (dtype == RS_F32) hipLaunchKernelGGL(upsample_fwd3_kernel<float>, grid, blk, smem / z + tab3, st, p);
-            else hipLaunchKernelGGL(upsample_fwd3_kernel<bf16_t>, grid, blk, smem / z + tab3, st, p);
-        } else {
-            if (dtype == RS_F32) hipLaunchKernelGGL(upsample_fwd2_kernel<float>, dim3(blocks, p.N), dim3(256), smem, st, p);
-            else hipLaunchKernelGGL(upsample_fwd2_kernel<bf16_t>, dim3(blocks, p.N), dim3(256), smem, st, p);
+int rs_launch_upsample(const UpParams& p, const GluePlan& pl, hipStream_t st, const void* u, int ldu, const float* mr, const float* gm) {
+    const dim3 grid(pl.bx, pl.by), blk(pl.threads);
+    switch (pl.kernel) {
+        case GLUE_UP_FWD: RS_GLUE_LAUNCH(upsample_fwd_kernel<T>, p) break;
+        case GLUE_UP_FWD2: RS_GLUE_LAUNCH(upsample_fwd2_kernel<T>, p) break;
+        case GLUE_UP_FWD3: RS_GLUE_LAUNCH(upsample_fwd3_kernel<T>, p) break;
+        case GLUE_UP_BWD: RS_GLUE_LAUNCH(upsample_bwd_kernel<T>, p) break;
+        case GLUE_UP_BWD2: RS_GLUE_LAUNCH(upsample_bwd2_kernel<T>, p) break;
+        case GLUE_UP_BWD4: {                                     // bf16 only; u set: p.y is a raw data gradient and the kernel applies its InstanceNorm backward tail
+            const UpInParams q = {p.y, p.ldy, p.dx, p.lddx, p.N, p.ID, p.IH, p.IW, p.OD, p.OH, p.OW, p.C, u, ldu, mr, gm};
+            if (u) {
+                if (pl.sel == 4) hipLaunchKernelGGL((upsample_bwd4_kernel<4, true>), grid, blk, 0, st, q, pl.arg);
+                else hipLaunchKernelGGL((upsample_bwd4_kernel<6, true>), grid, blk, 0, st, q, pl.arg);
+            } else {
+                if (pl.sel == 4) hipLaunchKernelGGL((upsample_bwd4_kernel<4, false>), grid, blk, 0, st, q, pl.arg);
+                else hipLaunchKernelGGL((upsample_bwd4_kernel<6, false>), grid, blk, 0, st, q, pl.arg);
+            }
+            break;
         }
-    } else {
-        static const bool v1 = getenv("RSUPER_UPSAMPLE_V1") != nullptr;
-        // contributing outputs per input index < 2 * (O-1)/(I-1) + 2: the table kernel holds 12 (up to 4x: the aux head); the
-        // first-generation kernel looks at 6 candidates (2x) and is kept for A/B runs only
-        auto ratio = [](int O, int I) { return I > 1 ? (double)(O - 1) / (double)(I - 1) : (double)O; };
-        const double rmax = fmax(ratio(p.OD, p.ID), fmax(ratio(p.OH, p.IH), ratio(p.OW, p.IW)));
-        if (!v1 && 2.0 * rmax + 2.0 > (double)UP_MAXW + 1e-9) return RS_ERR_UNSUPPORTED;
-        const int b = rs_elem_blocks((size_t)p.ID * p.IH * p.IW * CV);
-        const size_t tab = (size_t)(p.ID + p.IH + p.IW) * sizeof(UpEnt);
-        const bool small = (size_t)p.OD * p.OH * p.OW * p.ldy * (dtype == RS_F32 ? 4 : 2) < 0xFFFFFFFFull && (size_t)p.ID * p.IH * p.IW * CV < 0xFFFFFFFFull && tab <= 48 * 1024;
-        if (!v1 && dtype == RS_BF16) {                           // row-sharing kernel (upsample_bwd4_kernel)
-            const int rc = launch_upsample_bwd4(p.y, p.ldy, p.dx, p.lddx, p.N, p.ID, p.IH, p.IW, p.OD, p.OH, p.OW, p.C, st);
-            if (rc != RS_ERR_UNSUPPORTED) return rc;
-        }
-        if (v1 || !small) {
-            if (dtype == RS_F32) hipLaunchKernelGGL(upsample_bwd_kernel<float>, dim3(b, p.N), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL(upsample_bwd_kernel<bf16_t>, dim3(b, p.N), dim3(256), 0, st, p);
-        } else {
-            if (dtype == RS_F32) hipLaunchKernelGGL(upsample_bwd2_kernel<float>, dim3(b, p.N), dim3(256), tab, st, p);
-            else hipLaunchKernelGGL(upsample_bwd2_kernel<bf16_t>, dim3(b, p.N), dim3(256), tab, st, p);
-        }
+        default: return RS_ERR_UNSUPPORTED;
     }
     return rs_check_launch();
 }
+#undef RS_GLUE_LAUNCH
 
 #define RS_DISPATCH_C(KERNEL, T, C, ...)                                                        \
     switch (C) {                                                                                \
@@ -1738,7 +1561,7 @@ int rs_launch_stem(const StemParams& p, int dtype, int wgrad, hipStream_t st) {
     const int vox = p.D * p.H * p.W;
     if (!wgrad) {
         const size_t smem = (size_t)(256 * (p.C + 1)) * sizeof(float);
-        dim3 grid((vox + 255) / 256, p.N);
+        dim3 grid(rs_stat_rows(GLUE_OP_STEM_FWD, vox), p.N);       // the rows of `part` the caller allocated
         if (p.C <= 32 && (p.C % 4) == 0) {
             if (dtype == RS_F32) hipLaunchKernelGGL(stem_fwd_mfma_kernel<float>, grid, dim3(256), 0, st, p);
             else hipLaunchKernelGGL(stem_fwd_mfma_kernel<bf16_t>, grid, dim3(256), 0, st, p);

@@ -55,6 +55,8 @@ _SIGS = {
     'rsuper_pointwise_wgrad': (c_int, [c_int, P, c_int, P, c_int, c_long, c_int, c_int, P, c_int, P, P, P]),
     'rsuper_stats_finalize': (c_int, [P, c_int, c_int, c_int, c_double, c_float, c_int, c_int, P, P]),
     'rsuper_glue_variant': (c_int, [c_int]),
+    'rsuper_stat_rows': (c_int, [c_int, c_long]),
+    'rsuper_glue_plan': (c_int, [c_int, c_int, P, c_int, c_int, P]),
     'rsuper_in_bwd_finalize': (c_int, [c_int, P, c_int, P, c_int, P, P, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_fwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_bwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
@@ -190,6 +192,12 @@ _SIGS = {
 IGEMM_CLASSIC, IGEMM_PC, IGEMM_WS, IGEMM_KD, IGEMM_BOX = range(5)
 # plan[0] of rsuper_conv3_wgrad_plan
 WGRAD_TILE, WGRAD_2, WGRAD_SV = range(3)
+# `op` of rsuper_stat_rows / rsuper_glue_plan
+GLUE_IN_BWD, GLUE_POOL_FWD, GLUE_POOL_BWD, GLUE_SUB_FWD, GLUE_SUB_BWD, GLUE_UP_FWD, GLUE_UP_BWD, GLUE_STEM_FWD = range(8)
+# out[0] of rsuper_glue_plan: the __global__ of csrc/unet_misc.hip that runs
+GLUE_KERNELS = ('in_bwd_finalize_kernel', 'in_bwd_finalize2_kernel', 'maxpool_fwd_kernel', 'maxpool_fwd2_kernel', 'maxpool_bwd_kernel',
+                'subsample_fwd_kernel', 'subsample_bwd_kernel', 'upsample_fwd_kernel', 'upsample_fwd2_kernel', 'upsample_fwd3_kernel',
+                'upsample_bwd_kernel', 'upsample_bwd2_kernel', 'upsample_bwd4_kernel')
 
 ERR = {1: 'RSUPER_ERR_ARG', 2: 'RSUPER_ERR_LAUNCH', 3: 'RSUPER_ERR_UNSUPPORTED', 4: 'RSUPER_ERR_NO_DEVICE'}
 

@@ -747,7 +747,8 @@ _BB = BasicBlockFn        # the class itself: `BasicBlockFn` is rebound to the r
 
 # ------------------------------------------------------------------------------------------------ pool / upsample
 def _stat_blocks(ovox):
-    return max(1, min(2048, ovox // 64))
+    """Rows of `part` for a pool / subsample / trilinear forward over `ovox` output voxels (one answer for the three: csrc/glue_plan.hpp)."""
+    return _L().rsuper_stat_rows(_l.GLUE_POOL_FWD, ovox)
 
 
 def _maxpool_fwd(x):
@@ -981,7 +982,7 @@ class StemFn(torch.autograd.Function):
         N, _, D, H, W = img.shape
         C = w.shape[0]
         y = torch.empty((N, D, H, W, C), device=img.device, dtype=dtype)
-        blocks = -(-(D * H * W) // 256)
+        blocks = _L().rsuper_stat_rows(_l.GLUE_STEM_FWD, D * H * W)      # the grid rsuper_stem_fwd launches
         part = torch.empty((N, blocks, C, 2), device=img.device, dtype=torch.float32)
         _l.check(_L().rsuper_stem_fwd(_DT[dtype], _ptr(img), _ptr(w), _ptr(y), C, _ptr(part), N, D, H, W, C, _stream()), 'stem_fwd')
         mr = stats_finalize(part, D * H * W)

@@ -61,6 +61,10 @@ IN_BWD = [  # (mode, N, vox, C, number of added gradients)
     ('bf16', 2, 24 ** 3, 128, 1), ('bf16', 2, 24 ** 3, 256, 1), ('bf16', 2, 12 ** 3, 256, 0), ('bf16', 2, 12 ** 3, 320, 1), ('bf16', 2, 6 ** 3, 320, 0),
     ('bf16', 1, 7 * 9 * 11, 8, 1), ('bf16', 3, 37 * 41 * 43, 16, 2),
     ('f32', 2, 48 ** 3, 64, 1), ('f32', 2, 24 ** 3, 128, 0), ('f32', 1, 7 * 9 * 11, 8, 2),
+    # either side of the dispatch thresholds (csrc/glue_plan.hpp): 255 | 256, 1023 | 1024, 8192 | 8193 blocks' worth of vectors; vector counts per
+    # voxel that are no power of two
+    ('bf16', 1, 65280, 8, 0), ('bf16', 1, 65281, 8, 1), ('bf16', 1, 261888, 8, 0), ('bf16', 1, 261889, 8, 2), ('bf16', 1, 2097152, 8, 1),
+    ('bf16', 1, 2097153, 8, 0), ('bf16', 1, 48 ** 3, 24, 1), ('bf16', 1, 24 ** 3, 320, 0),
 ]
 
 
@@ -104,6 +108,9 @@ POOL = [  # (mode, N, (D, H, W), C)
     ('bf16', 2, (96, 96, 96), 32), ('bf16', 2, (48, 48, 48), 64), ('bf16', 2, (24, 24, 24), 128), ('bf16', 2, (12, 12, 12), 256),
     ('bf16', 1, (7, 9, 11), 8), ('bf16', 1, (6, 10, 14), 8), ('bf16', 3, (10, 6, 14), 320),
     ('f32', 2, (24, 24, 24), 128), ('f32', 2, (12, 12, 12), 256), ('f32', 1, (7, 9, 11), 8),
+    # 1008 | 1024 statistics rows forward, 496 | 512 blocks backward; the channel split at 24^3 and 12^3
+    ('bf16', 1, (126, 64, 64), 8), ('bf16', 1, (128, 64, 64), 8), ('bf16', 1, (128, 128, 62), 8), ('bf16', 1, (128, 128, 64), 8),
+    ('bf16', 2, (24, 24, 24), 256), ('bf16', 2, (24, 24, 24), 320), ('bf16', 2, (12, 12, 12), 128), ('bf16', 2, (12, 12, 12), 320),
 ]
 
 
@@ -136,7 +143,9 @@ def test_maxpool_matches_previous_kernel(mode, N, dims, C):
 
 
 @pytest.mark.parametrize('mode,N,dims,C', [('bf16', 2, (48, 48, 48), 64), ('bf16', 2, (24, 24, 24), 128), ('bf16', 2, (12, 12, 12), 256),
-                                           ('bf16', 1, (7, 9, 11), 8), ('f32', 2, (12, 12, 12), 256), ('f32', 1, (7, 9, 11), 8)])
+                                           ('bf16', 1, (7, 9, 11), 8), ('f32', 2, (12, 12, 12), 256), ('f32', 1, (7, 9, 11), 8),
+                                           ('bf16', 2, (24, 24, 24), 256), ('bf16', 2, (24, 24, 24), 320), ('bf16', 2, (12, 12, 12), 128),
+                                           ('bf16', 2, (12, 12, 12), 320)])
 def test_subsample_matches_previous_kernel(mode, N, dims, C):
     from rsuper_amd.hip import ops, lib
     dt = DTS[mode]
@@ -159,6 +168,8 @@ UP = [  # (mode, N, input dims, output dims, C)
     ('bf16', 2, (6, 6, 6), (12, 12, 12), 320), ('bf16', 1, (3, 5, 4), (7, 9, 11), 8), ('bf16', 1, (5, 1, 7), (5, 4, 7), 8),
     ('f32', 2, (12, 12, 12), (24, 24, 24), 256), ('f32', 2, (24, 24, 24), (48, 48, 48), 128), ('f32', 2, (6, 6, 6), (12, 12, 12), 320),
     ('f32', 1, (3, 5, 4), (7, 9, 11), 8),
+    # the per-axis tables of upsample_fwd3 stop fitting 64 KB next to the statistics scratch between 3070 and 3071 outputs
+    ('bf16', 1, (1, 1, 1536), (1, 1, 3070), 8), ('bf16', 1, (1, 1, 1536), (1, 1, 3071), 8),
 ]
 
 
