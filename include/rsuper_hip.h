@@ -259,6 +259,21 @@ int rsuper_stat_rows(int op, long vox);
  * NT of upsample_bwd4, else 0), blocks in x, y, z, threads per block, dynamic LDS bytes, rows of `part` (rsuper_stat_rows; 0: none).
  * RSUPER_ERR_UNSUPPORTED where the launch would answer it, RSUPER_ERR_ARG for arguments that describe no launch. */
 int rsuper_glue_plan(int op, int dtype, const int* shape, int C, int ld, int* out);
+/* The same for the kernels MedFormer's attention stages run on (1x1x1 convolution GEMM and its weight gradient, depthwise 3x3x3, channel norm,
+ * squeeze-excite, rsuper_cl_planar): csrc/mf_plan.hpp is the one place that decides, one `op` per launch.  shape: K, N (PW_PACK); fragment slots
+ * (PW_PACK_BATCH); R, K, N (PW, either mode); R, N, K (PW_WGRAD*); N, D, H, W, C (DW*); N, vox, C, mode (CNORM*; CNORM is the first launch of
+ * rsuper_cnorm_forward (mode 0) / _backward (mode 1)); N, C, r (SE_*); N, vox, C, K (CL_PLANAR).
+ * out[10]: kernel (0 pw_pack, 1 pw_pack_batch, 2 pw_gemm, 3 pw_wgrad, 4 pw_wgrad_reduce, 5 depthwise_fwd, 6 depthwise_lds, 7 depthwise_wgrad,
+ * 8 depthwise_wgrad_reduce, 9 cnorm_stats, 10 cnorm_apply, 11 cnorm_small, 12 se_hidden_fwd, 13 se_gate_fwd, 14 se_excite_bwd_hidden, 15 se_excite_wgrad,
+ * 16 se_dm, 17 cl_planar; -1 with RSUPER_OK: PW_WGRAD_REDUCE of a single slab, no launch), template selector (NF of pw_gemm, WNW of pw_wgrad, MODE of
+ * cnorm_*), blocks in x, y, z, threads per block, dynamic LDS bytes, rows (of `part`: cnorm statistics, depthwise weight gradient; slabs of the
+ * pw_wgrad workspace; 0: none), the kernel argument that goes with the grid (KSPLIT of pw_gemm, rows per slab of pw_wgrad, D segments of
+ * depthwise_lds), and what the caller allocates (bytes of PW_PACK's fragments, floats of PW_WGRAD's workspace, else 0).  dtype: the compute type of
+ * the pointwise kernels; storage is f32 throughout.  Errors as rsuper_glue_plan; an error leaves `out` untouched. */
+enum { RSUPER_MF_PW_PACK = 0, RSUPER_MF_PW_PACK_BATCH, RSUPER_MF_PW, RSUPER_MF_PW_WGRAD, RSUPER_MF_PW_WGRAD_REDUCE, RSUPER_MF_DW, RSUPER_MF_DW_WGRAD,
+       RSUPER_MF_DW_WGRAD_REDUCE, RSUPER_MF_CNORM, RSUPER_MF_CNORM_STATS, RSUPER_MF_CNORM_APPLY, RSUPER_MF_SE_HIDDEN, RSUPER_MF_SE_GATE,
+       RSUPER_MF_SE_BWD_HIDDEN, RSUPER_MF_SE_WGRAD, RSUPER_MF_SE_DM, RSUPER_MF_CL_PLANAR };
+int rsuper_mf_plan(int op, int dtype, const int* shape, int* out);
 /* dx = rstd * (g - gm0 - x_n * gm1) [+ add1] [+ add2] */
 int rsuper_in_bwd_finalize(int dtype, const void* g, int ldg, const void* x, int ldx, const float* mr, const float* gm,
                            const void* add1, int lda1, const void* add2, int lda2, void* out, int ldo,
@@ -391,13 +406,15 @@ int rsuper_window_normalize(float* acc, const float* cd, const float* ch, const 
  *        mode 2 out = x * mr[1] + mr[0]: a per-(sample, channel) affine map (SEBlock scaling x * s and its gradient, conv_layers.py:159-174).
  * ------------------------------------------------------------------------------------------------ */
 int rsuper_cnorm_rows(long vox);
-/* one-launch variant for small volumes (statistics + finalize + apply in a block per (sample, 64 channels)):
+/* one-launch kernel (statistics + finalize + apply in a block per (sample, 16 channels)), at any size:
  * mode 0: out = norm(x) [+ relu], mr_out = (mean, rstd);  mode 1: out = dx from (x, dy, mr). */
 int rsuper_cnorm_small(const float* x, const float* dy, const float* mr, float* out, float* mr_out, int N, long vox, int C, int relu, float eps,
                        int mode, void* stream);
 int rsuper_cnorm_stats(const float* x, const float* dy, const float* mr, float* part, int N, long vox, int C, int relu, int mode, void* stream);
-/* stats -> rsuper_stats_finalize -> apply in one host call (same three launches; part / mr / gm as above): forward writes mr and
- * y = norm(x) [+ relu]; backward writes gm and dx. */
+/* A whole norm in one host call: forward writes mr and y = norm(x) [+ relu]; backward writes dx.  Small volumes (up to RSUPER_CNORM_SMALL_VOX = 512
+ * voxels) take the one-launch kernel, the others stats -> rsuper_stats_finalize -> apply (part / mr / gm as above; backward writes gm).
+ * rsuper_cnorm_part_rows: the rows of `part` these two want, 0 where the one launch runs: part (and gm) are then not read and may be NULL. */
+int rsuper_cnorm_part_rows(long vox);
 int rsuper_cnorm_forward(const float* x, float* part, float* mr, float* y, int N, long vox, int C, int relu, float eps, void* stream);
 int rsuper_cnorm_backward(const float* x, const float* dy, const float* mr, float* part, float* gm, float* dx, int N, long vox, int C, int relu,
                           void* stream);

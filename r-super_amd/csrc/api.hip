@@ -23,6 +23,7 @@ static inline bool pack_range_ok(int mode, int na, int nb) { return mode != 1 ||
 #include "igemm_plan.hpp"      // which kernel / block width / statistics rows a 3x3x3 igemm launch gets: igemm_plan, s2_kernel (needs dt_ok, bn_ok)
 #include "wgrad_plan.hpp"      // which kernel / configuration / split count a 3x3x3 weight-gradient launch gets: wgrad_plan (needs dt_ok)
 #include "glue_plan.hpp"       // which kernel / grid / LDS / statistics rows a launch of the bandwidth-bound glue kernels gets: glue_*_plan (needs dt_ok)
+#include "mf_plan.hpp"         // which kernel / grid / rows / workspace a launch of the pointwise, depthwise and channel-norm kernels gets: mf_*_plan (needs dt_ok)
 #include "lazy_tail_plan.hpp"  // which InstanceNorm backward tails run inside the kernel that consumes them: lazy_pool_plan (needs dt_ok, glue_up_bwd_plan)
 
 // ---- optimiser: split the tensor list into kernel-argument sized chunks
@@ -374,27 +375,28 @@ int rsuper_conv3_wgrad_s2(int dtype, const void* xa, int lda, int Ca, const floa
     return rs_launch_wgrad_s2(p, dtype, ST(stream));
 }
 
-size_t rsuper_pointwise_packed_bytes(int dtype, int K, int N) { return dt_ok(dtype) && K > 0 && N > 0 ? rs_pw_packed_bytes(N, K, dtype) : 0; }
+size_t rsuper_pointwise_packed_bytes(int dtype, int K, int N) { return dt_ok(dtype) && K > 0 && N > 0 ? mf_pw_packed_bytes(dtype, K, N) : 0; }
 int rsuper_pointwise(int dtype, int mode, const float* x, int ldx, const float* w, const float* bias, const float* res, int ldr,
                      float* y, int ldy, long R, int K, int N, void* packed, void* stream) {
     if (!dt_ok(dtype) || (mode != 0 && mode != 1) || !x || !y || !packed || R <= 0 || K <= 0 || N <= 0) return RS_ERR_ARG;   // w == nullptr: `packed` already holds the fragments
     if ((N % 4) || (ldx % 4) || (ldy % 4) || ldx < K || ldy < N || (mode == 1 && bias)) return RS_ERR_ARG;
     if (res && ((ldr % 4) || ldr < N)) return RS_ERR_ARG;
     if ((unsigned long long)R * ldx * 4ull >= (1ull << 32) || R > 0x7FFFFFFFl) return RS_ERR_UNSUPPORTED;   // buffer-addressed operand loads
-    return rs_launch_pointwise(dtype, mode, x, ldx, w, bias, res, ldr, y, ldy, (int)R, K, N, packed, ST(stream));
+    return rs_launch_pointwise(mode, x, ldx, w, bias, res, ldr, y, ldy, (int)R, K, N, packed, mf_pw_pack_plan(dtype, K, N), mf_pw_plan(dtype, (int)R, K, N), ST(stream));
 }
 
 int rsuper_pointwise_pack_batch(int dtype, const long long* table, int n, long total_items, void* arena, void* stream) {
     if (!dt_ok(dtype) || !table || n <= 0 || total_items <= 0 || !arena) return RS_ERR_ARG;
-    return rs_launch_pointwise_pack_batch(dtype, table, n, total_items, arena, ST(stream));
+    return rs_launch_pointwise_pack_batch(table, n, total_items, arena, mf_pw_pack_batch_plan(dtype, total_items), ST(stream));
 }
-int rsuper_pointwise_wgrad_splits(long R, int N, int K) { return (R > 0 && R <= 0x7FFFFFFFl && N > 0 && K > 0) ? rs_pw_wgrad_splits((int)R, N, K) : 0; }
+int rsuper_pointwise_wgrad_splits(long R, int N, int K) { return (R > 0 && R <= 0x7FFFFFFFl && N > 0 && K > 0) ? mf_pw_wgrad_plan(RS_BF16, (int)R, N, K, 0).rows : 0; }
 int rsuper_pointwise_wgrad(int dtype, const float* dy, int ldy, const float* x, int ldx, long R, int N, int K, float* workspace, int splits,
                            float* dw, float* db, void* stream) {
     if (!dt_ok(dtype) || !dy || !x || !workspace || !dw || R <= 0 || N <= 0 || K <= 0 || splits <= 0) return RS_ERR_ARG;
     if ((N % 4) || (K % 4) || ldy < N || ldx < K) return RS_ERR_ARG;
     if ((unsigned long long)(R + 1) * ldx * 4ull >= (1ull << 32) || (unsigned long long)(R + 1) * ldy * 4ull >= (1ull << 32)) return RS_ERR_UNSUPPORTED;
-    return rs_launch_pointwise_wgrad(dtype, dy, ldy, x, ldx, (int)R, N, K, workspace, splits, dw, db, ST(stream));
+    const GluePlan pl = mf_pw_wgrad_plan(dtype, (int)R, N, K, splits);      // the workspace holds `splits` slabs: rsuper_pointwise_wgrad_splits, or any other count
+    return rs_launch_pointwise_wgrad(dy, ldy, x, ldx, (int)R, N, K, workspace, dw, db, pl, mf_pw_wgrad_reduce_plan(N, K, pl.rows), ST(stream));
 }
 
 int rsuper_stats_finalize(const float* part, int N, int nblk, int C, double cnt, float eps, int mode, int split, float* out, void* stream) {
@@ -409,6 +411,15 @@ int rsuper_glue_plan(int op, int dtype, const int* shape, int C, int ld, int* ou
     if (!out) return RS_ERR_ARG;
     if (const int rc = glue_plan_query(op, dtype, shape, C, ld, &pl)) return rc;
     out[0] = pl.kernel; out[1] = pl.sel; out[2] = pl.bx; out[3] = pl.by; out[4] = pl.bz; out[5] = pl.threads; out[6] = pl.lds; out[7] = pl.rows;
+    return RS_OK;
+}
+int rsuper_mf_plan(int op, int dtype, const int* shape, int* out) {
+    GluePlan pl;
+    long ws;
+    if (!out) return RS_ERR_ARG;
+    if (const int rc = mf_plan_query(op, dtype, shape, &pl, &ws)) return rc;
+    out[0] = pl.kernel; out[1] = pl.sel; out[2] = pl.bx; out[3] = pl.by; out[4] = pl.bz; out[5] = pl.threads; out[6] = pl.lds; out[7] = pl.rows;
+    out[8] = pl.arg; out[9] = (int)ws;
     return RS_OK;
 }
 
@@ -572,42 +583,49 @@ int rsuper_plane_partials_bwd2(const float* x, size_t xstride, const uint8_t* t,
     PlaneParams p = {x, xstride, t, k, w1, w2, nullptr, g, dx, flags & 1, V, k ? (flags >> 1) & 1 : 0, tpk, tP, tC, kflags};
     return rs_launch_plane_partials(p, planes, 1, ST(stream));
 }
-int rsuper_cnorm_rows(long vox) { return rs_cnorm_rows(vox); }
+int rsuper_cnorm_rows(long vox) { return mf_cnorm_rows(vox); }
+int rsuper_cnorm_part_rows(long vox) { return vox > 0 ? mf_cnorm_plan(1, vox, 4, 0).rows : 0; }
 int rsuper_cnorm_stats(const float* x, const float* dy, const float* mr, float* part, int N, long vox, int C, int relu, int mode, void* stream) {
     if (!x || !part || N <= 0 || vox <= 0 || C <= 0 || (C & 3) || (mode != 0 && mode != 1) || (mode == 1 && (!dy || !mr))) return RS_ERR_ARG;
-    return rs_launch_cnorm_stats(x, dy, mr, part, N, vox, C, relu ? 1 : 0, mode, ST(stream));
+    return rs_launch_cnorm_stats(x, dy, mr, part, N, vox, C, relu ? 1 : 0, mf_cnorm_stats_plan(N, vox, C, mode), ST(stream));
 }
 int rsuper_cnorm_apply(const float* x, const float* dy, const float* mr, const float* gm, float* out, int N, long vox, int C, int relu, int mode,
                        void* stream) {
     if (!x || !mr || !out || N <= 0 || vox <= 0 || C <= 0 || (C & 3) || mode < 0 || mode > 2 || (mode == 1 && (!dy || !gm))) return RS_ERR_ARG;
-    return rs_launch_cnorm_apply(x, dy, mr, gm, out, N, vox, C, relu ? 1 : 0, mode, ST(stream));
+    return rs_launch_cnorm_apply(x, dy, mr, gm, out, N, vox, C, relu ? 1 : 0, mf_cnorm_apply_plan(N, vox, C, mode), ST(stream));
 }
-/* statistics -> finalize -> apply as ONE host call (three launches): the eager training step of MedFormer is bound by the host's
- * per-call cost (230 norm calls per step), not by these kernels */
+// statistics -> finalize -> apply of a channel norm as ONE host call, mode 0: forward, 1: backward (out = dx, mr2 = the backward means)
+static int cnorm_three_launches(const float* x, const float* dy, const float* mr, float* part, float* mr2, float* out, int N, long vox, int C, int relu, float eps,
+                                const GluePlan& stats, int mode, hipStream_t st) {
+    int rc = rs_launch_cnorm_stats(x, dy, mr, part, N, vox, C, relu, stats, st);
+    if (rc != RS_OK) return rc;
+    rc = rs_launch_stats_finalize(part, N, stats.rows, C, (double)vox, eps, mode, 0, mr2, st);
+    if (rc != RS_OK) return rc;
+    return rs_launch_cnorm_apply(x, dy, mode ? mr : mr2, mode ? mr2 : nullptr, out, N, vox, C, relu, mf_cnorm_apply_plan(N, vox, C, mode), st);
+}
+/* A whole norm as ONE host call, one launch or three as mf_cnorm_plan says: the eager training step of MedFormer is bound by the host's
+ * per-call cost (230 norm calls per step), not by these kernels.  part: rsuper_cnorm_part_rows(vox) rows; the one-launch path reads none */
 int rsuper_cnorm_forward(const float* x, float* part, float* mr, float* y, int N, long vox, int C, int relu, float eps, void* stream) {
-    if (!x || !part || !mr || !y || N <= 0 || vox <= 0 || C <= 0 || (C & 3)) return RS_ERR_ARG;
-    const int rows = rs_cnorm_rows(vox);
-    int rc = rs_launch_cnorm_stats(x, nullptr, nullptr, part, N, vox, C, relu ? 1 : 0, 0, ST(stream));
-    if (rc != RS_OK) return rc;
-    rc = rs_launch_stats_finalize(part, N, rows, C, (double)vox, eps, 0, 0, mr, ST(stream));
-    if (rc != RS_OK) return rc;
-    return rs_launch_cnorm_apply(x, nullptr, mr, nullptr, y, N, vox, C, relu ? 1 : 0, 0, ST(stream));
+    if (!x || !mr || !y || N <= 0 || vox <= 0 || C <= 0 || (C & 3)) return RS_ERR_ARG;
+    const GluePlan pl = mf_cnorm_plan(N, vox, C, 0);
+    if (pl.kernel == MF_CNORM_SMALL) return rs_launch_cnorm_small(x, nullptr, nullptr, y, mr, N, vox, C, relu ? 1 : 0, eps, pl, ST(stream));
+    if (!part) return RS_ERR_ARG;
+    return cnorm_three_launches(x, nullptr, nullptr, part, mr, y, N, vox, C, relu ? 1 : 0, eps, pl, 0, ST(stream));
 }
 int rsuper_cnorm_backward(const float* x, const float* dy, const float* mr, float* part, float* gm, float* dx, int N, long vox, int C, int relu,
                           void* stream) {
-    if (!x || !dy || !mr || !part || !gm || !dx || N <= 0 || vox <= 0 || C <= 0 || (C & 3)) return RS_ERR_ARG;
-    const int rows = rs_cnorm_rows(vox);
-    int rc = rs_launch_cnorm_stats(x, dy, mr, part, N, vox, C, relu ? 1 : 0, 1, ST(stream));
-    if (rc != RS_OK) return rc;
-    rc = rs_launch_stats_finalize(part, N, rows, C, (double)vox, 0.f, 1, 0, gm, ST(stream));
-    if (rc != RS_OK) return rc;
-    return rs_launch_cnorm_apply(x, dy, mr, gm, dx, N, vox, C, relu ? 1 : 0, 1, ST(stream));
+    if (!x || !dy || !mr || !dx || N <= 0 || vox <= 0 || C <= 0 || (C & 3)) return RS_ERR_ARG;
+    const GluePlan pl = mf_cnorm_plan(N, vox, C, 1);
+    if (pl.kernel == MF_CNORM_SMALL) return rs_launch_cnorm_small(x, dy, mr, dx, nullptr, N, vox, C, relu ? 1 : 0, 0.f, pl, ST(stream));
+    if (!part || !gm) return RS_ERR_ARG;
+    return cnorm_three_launches(x, dy, mr, part, gm, dx, N, vox, C, relu ? 1 : 0, 0.f, pl, 1, ST(stream));
 }
+/* the one-launch kernel at any size (tests, measurements): rsuper_cnorm_forward / _backward take it where the plan says so */
 int rsuper_cnorm_small(const float* x, const float* dy, const float* mr, float* out, float* mr_out, int N, long vox, int C, int relu, float eps,
                        int mode, void* stream) {
     if (!x || !out || N <= 0 || vox <= 0 || C <= 0 || (C & 3) || (mode != 0 && mode != 1) || (mode == 0 && !mr_out) || (mode == 1 && (!dy || !mr)))
         return RS_ERR_ARG;
-    return rs_launch_cnorm_small(x, dy, mr, out, mr_out, N, vox, C, relu ? 1 : 0, eps, mode, ST(stream));
+    return rs_launch_cnorm_small(x, dy, mr, out, mr_out, N, vox, C, relu ? 1 : 0, eps, mf_cnorm_small_plan(N, C, mode), ST(stream));
 }
 int rsuper_token_attn_supported(int L, int dim_head) { return rs_token_attn_supported(L, dim_head); }
 int rsuper_token_attn_fwd(const float* qkv, float* o, float* p, int B, int L, int heads, int dim_head, float scale, void* stream) {
@@ -633,31 +651,51 @@ int rsuper_battn_bwd(const float* fqv, const float* mqv, const float* m_out, con
     return rs_launch_battn(fqv, mqv, nullptr, (float*)m_out, (float*)lse, d_f_out, d_m_out, d_fqv, d_mqv, part, nullptr, B, L, T, heads, dim_head,
                            scale, 1, ST(stream));
 }
+// SEBlock forward in one host call: channel means (statistics + finalize), excitation, y = x * s.  scratch: part (cnorm rows), ms (N, C, 2),
+// tab (N, C, 2) = (0, s) and hbuf (N, r) are kept by the caller for the backward pass.
 int rsuper_se_forward(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* part, float* ms, float* tab,
                       float* hbuf, float* y, int N, long vox, int C, int r, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !part || !ms || !tab || !hbuf || !y || N <= 0 || vox <= 0 || C <= 0 || (C & 3) || r <= 0) return RS_ERR_ARG;
-    return rs_launch_se_forward(x, w1, b1, w2, b2, part, ms, tab, hbuf, y, N, vox, C, r, ST(stream));
+    const GluePlan hidden = mf_se_plan(MF_SE_HIDDEN_FWD, N, C, r), stats = mf_cnorm_stats_plan(N, vox, C, 0);
+    if (hidden.kernel == MF_NONE) return RS_ERR_UNSUPPORTED;
+    int rc = rs_launch_cnorm_stats(x, nullptr, nullptr, part, N, vox, C, 0, stats, ST(stream));
+    if (rc != RS_OK) return rc;
+    rc = rs_launch_stats_finalize(part, N, stats.rows, C, (double)vox, 0.f, 1, 0, ms, ST(stream));
+    if (rc != RS_OK) return rc;
+    rc = rs_launch_se_excite(ms, w1, b1, w2, b2, hbuf, tab, C, r, hidden, mf_se_plan(MF_SE_GATE_FWD, N, C, r), ST(stream));
+    if (rc != RS_OK) return rc;
+    return rs_launch_cnorm_apply(x, nullptr, tab, nullptr, y, N, vox, C, 0, mf_cnorm_apply_plan(N, vox, C, 2), ST(stream));
 }
+// SEBlock backward in one host call.  ident: (N, C, 2) table of (0, 1) (the statistics kernel then yields the means of (dy, dy * x)).
 int rsuper_se_backward(const float* x, const float* dy, const float* ident, const float* w1, const float* w2, const float* ms, const float* tab,
                        const float* hbuf, float* part, float* gm, float* dz1, float* tab2, float* dx, float* dw1, float* db1, float* dw2, float* db2,
                        int N, long vox, int C, int r, void* stream) {
     if (!x || !dy || !ident || !w1 || !w2 || !ms || !tab || !hbuf || !part || !gm || !dz1 || !tab2 || !dx || !dw1 || !db1 || !dw2 || !db2 ||
         N <= 0 || vox <= 0 || C <= 0 || (C & 3) || r <= 0)
         return RS_ERR_ARG;
-    return rs_launch_se_backward(x, dy, ident, w1, w2, ms, tab, hbuf, part, gm, dz1, tab2, dx, dw1, db1, dw2, db2, N, vox, C, r, ST(stream));
+    const GluePlan hidden = mf_se_plan(MF_SE_BWD_HIDDEN, N, C, r), stats = mf_cnorm_stats_plan(N, vox, C, 1);
+    if (hidden.kernel == MF_NONE) return RS_ERR_UNSUPPORTED;
+    int rc = rs_launch_cnorm_stats(x, dy, ident, part, N, vox, C, 0, stats, ST(stream));
+    if (rc != RS_OK) return rc;
+    rc = rs_launch_stats_finalize(part, N, stats.rows, C, (double)vox, 0.f, 1, 0, gm, ST(stream));
+    if (rc != RS_OK) return rc;
+    rc = rs_launch_se_excite_bwd(gm, tab, hbuf, ms, w1, w2, dz1, tab2, dw1, db1, dw2, db2, N, vox, C, r, hidden, mf_se_plan(MF_SE_WGRAD, N, C, r),
+                                 mf_se_plan(MF_SE_DM, N, C, r), ST(stream));
+    if (rc != RS_OK) return rc;
+    return rs_launch_cnorm_apply(dy, nullptr, tab2, nullptr, dx, N, vox, C, 0, mf_cnorm_apply_plan(N, vox, C, 2), ST(stream));
 }
 int rsuper_cl_planar(const float* src, float* dst, int N, long vox, int C, int K, int to_channels_last, void* stream) {
     if (!src || !dst || N <= 0 || vox <= 0 || C <= 0 || K <= 0) return RS_ERR_ARG;
-    return rs_launch_cl_planar(src, dst, N, vox, C, K, to_channels_last ? 1 : 0, ST(stream));
+    return rs_launch_cl_planar(src, dst, N, vox, C, K, to_channels_last ? 1 : 0, mf_cl_planar_plan(N, vox, C, K), ST(stream));
 }
-int rsuper_depthwise3_rows(long vox) { return rs_depthwise_rows(vox); }
+int rsuper_depthwise3_rows(long vox) { return mf_dw_rows(vox); }
 int rsuper_depthwise3_fwd(const float* x, const float* w, float* y, int N, int D, int H, int W, int C, int flip, void* stream) {
     if (!x || !w || !y || N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || (flip != 0 && flip != 1)) return RS_ERR_ARG;
-    return rs_launch_depthwise(x, w, y, N, D, H, W, C, flip, ST(stream));
+    return rs_launch_depthwise(x, w, y, N, D, H, W, C, flip, mf_dw_plan(N, D, H, W, C), ST(stream));
 }
 int rsuper_depthwise3_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int D, int H, int W, int C, void* stream) {
     if (!x || !dy || !part || !dw || N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return RS_ERR_ARG;
-    return rs_launch_depthwise_wgrad(x, dy, part, dw, N, D, H, W, C, ST(stream));
+    return rs_launch_depthwise_wgrad(x, dy, part, dw, N, D, H, W, C, mf_dw_wgrad_plan(N, D, H, W, C), mf_dw_wgrad_reduce_plan(N, D, H, W, C), ST(stream));
 }
 int rsuper_seg_from_sums(const float* sums, const float* cw, int B, int C, size_t V, double scale, float* loss, float* dsums, void* stream) {
     if (!sums || !loss || !dsums || B <= 0 || C <= 0 || V == 0) return RS_ERR_ARG;

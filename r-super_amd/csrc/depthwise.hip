@@ -13,11 +13,9 @@
 // (2.4-2.9 ms per call; 1.2 s per training step at 96^3).
 #include "common.hpp"
 #include "misc.hpp"
+#include "mf_tiles.hpp"      // DW_CG, DW_VPB, DW_R, DL_T, DL_C
 
 namespace {
-
-constexpr int DW_CG = 64;              // channels per block
-constexpr int DW_VPB = 16;             // voxels per pass: 256 threads = 16 voxels x 16 channel vectors
 
 struct DwParams {
     const float* x;        // [N][D][H][W][C] input (forward) / dy (data gradient)
@@ -29,8 +27,7 @@ struct DwParams {
 
 // Each thread produces DW_R consecutive outputs along W for its 4 channels: a (kd, kh) row of the halo is DW_R + 2 vectors that feed
 // 3 * DW_R multiply-adds each, i.e. 9 * (DW_R + 2) loads per DW_R outputs instead of 27 per output (2x fewer at DW_R = 4) -- the kernel
-// is bound by L1 / L2 transactions, not by HBM.
-constexpr int DW_R = 4;
+// is bound by L1 / L2 transactions, not by HBM.  (DW_R = 4: mf_tiles.hpp)
 
 // XCD-aware work order.  Workgroups are dealt round-robin to the 8 XCDs (each with its own 4 MB L2): with a plain grid-stride loop the
 // blocks of one XCD touch every 8th group of runs, so each L2 holds its own copy of every halo plane (measured 6x the algorithmic
@@ -127,8 +124,6 @@ __global__ __launch_bounds__(256, 2) void depthwise_fwd_kernel(DwParams p) {
 // stencil reads LDS.  Thread = (4 outputs along W, 4 channels), 128 threads per block; global loads run two planes ahead of the
 // stencil in registers and land in LDS when their slot is free (two barriers per plane).  Row layout in LDS: one pad voxel after every
 // four, so the two 4-voxel runs of a row that a 16-lane group reads together start 640 bytes apart and use disjoint banks.
-constexpr int DL_T = 8;                                  // tile edge in H and W
-constexpr int DL_C = 32;                                 // channels per block
 constexpr int DL_ROW = 12;                               // LDS slots per halo row: 10 voxels + a pad slot after every 4
 constexpr int DL_PLANE = (DL_T + 2) * DL_ROW;            // slots per halo plane
 
@@ -357,42 +352,24 @@ __global__ __launch_bounds__(256) void depthwise_wgrad_reduce_kernel(const float
 
 }  // namespace
 
-int rs_depthwise_rows(long vox) {
-    long b = (vox + DW_VPB * 8 - 1) / (DW_VPB * 8);                   // >= 8 passes per block
-    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-
-int rs_launch_depthwise(const float* x, const float* w, float* y, int N, int D, int H, int W, int C, int flip, hipStream_t st) {
-    if ((long)N * D * H * W * C >= (1L << 30)) return RS_ERR_UNSUPPORTED;       // 32-bit byte offsets of the buffer loads (< 4 GiB)
+// forward (flip 0) and data gradient (flip 1): the LDS-tiled kernel on its (tiles x D segments, channel groups, N) grid, or the register-run kernel
+int rs_launch_depthwise(const float* x, const float* w, float* y, int N, int D, int H, int W, int C, int flip, const GluePlan& pl, hipStream_t st) {
     DwParams p = {x, w, y, N, D, H, W, C, flip};
-    const long vox = (long)N * D * H * W;
-    static const bool no_lds = getenv("RSUPER_DW_NO_LDS") != nullptr;          // A/B switch: the register-run kernel for every shape
-    // measured (B = 2): 48^3 x 256 ch 209 -> 149 us; 24^3 x 512 41 -> 40, 24^3 x 384 33 -> 37, 24^3 x 128 14 -> 20 us (the halo planes of the
-    // short D segments and 6 waves per CU cost more than the L2 re-reads there): the LDS kernel takes the 32^2-and-larger planes only
-    if (!no_lds && H >= 32 && W >= 32 && D >= 6 && (C % 4) == 0 && (size_t)H * W * C * 4 < 0x40000000ull) {
-        const int th = (H + DL_T - 1) / DL_T, tw = (W + DL_T - 1) / DL_T, groups = (C + DL_C - 1) / DL_C;
-        // split D so that >= ~1500 blocks are in flight (3 per CU), but keep >= 6 planes per segment (2 halo planes are re-read per segment)
-        int dsegs = 1;
-        while ((long)th * tw * groups * N * dsegs < 1536 && D / (dsegs + 1) >= 6) ++dsegs;
-        hipLaunchKernelGGL(depthwise_lds_kernel, dim3((unsigned)(th * tw * dsegs), groups, N), dim3(128), 0, st, p, dsegs, tw, th);
-        return rs_check_launch();
+    const dim3 grid((unsigned)pl.bx, (unsigned)pl.by, (unsigned)pl.bz);
+    switch (pl.kernel) {
+        case MF_DW_LDS: hipLaunchKernelGGL(depthwise_lds_kernel, grid, dim3(pl.threads), 0, st, p, pl.arg, (W + DL_T - 1) / DL_T, (H + DL_T - 1) / DL_T); break;
+        case MF_DW_FWD: hipLaunchKernelGGL(depthwise_fwd_kernel, grid, dim3(pl.threads), 0, st, p); break;
+        default: return RS_ERR_UNSUPPORTED;
     }
-    const long runs = (long)N * D * H * ((W + DW_R - 1) / DW_R);
-    // the LDS weight staging is per block: aim at >= 8 passes per block, but never below ~1024 blocks in flight (small volumes)
-    const long groups = (C + DW_CG - 1) / DW_CG, all = (runs + DW_VPB - 1) / DW_VPB;
-    long bx = (runs + DW_VPB * 8 - 1) / (DW_VPB * 8);
-    if (bx * groups < 1024) bx = (1024 + groups - 1) / groups;
-    if (bx > all) bx = all;
-    if (bx > 2048) bx = 2048;
-    hipLaunchKernelGGL(depthwise_fwd_kernel, dim3((unsigned)bx, (C + DW_CG - 1) / DW_CG), dim3(256), 0, st, p);
     return rs_check_launch();
 }
 
-int rs_launch_depthwise_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int D, int H, int W, int C, hipStream_t st) {
-    if ((long)N * D * H * W * C >= (1L << 30)) return RS_ERR_UNSUPPORTED;
-    const int rows = rs_depthwise_rows((long)N * D * H * W);
+// part: pl.rows x 27 x C partial rows, summed in row order by the second launch
+int rs_launch_depthwise_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int D, int H, int W, int C, const GluePlan& pl,
+                              const GluePlan& reduce, hipStream_t st) {
+    if (pl.kernel != MF_DW_WGRAD || reduce.kernel != MF_DW_WGRAD_REDUCE) return RS_ERR_UNSUPPORTED;
     DwWgParams p = {x, dy, part, N, D, H, W, C};
-    hipLaunchKernelGGL(depthwise_wgrad_kernel, dim3(rows, (C + DW_CG - 1) / DW_CG), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(depthwise_wgrad_reduce_kernel, dim3((27 * C + 31) / 32), dim3(256), 0, st, (const float*)part, rows, C, dw);
+    hipLaunchKernelGGL(depthwise_wgrad_kernel, dim3(pl.bx, pl.by), dim3(pl.threads), 0, st, p);
+    hipLaunchKernelGGL(depthwise_wgrad_reduce_kernel, dim3(reduce.bx), dim3(reduce.threads), 0, st, (const float*)part, pl.rows, C, dw);
     return rs_check_launch();
 }

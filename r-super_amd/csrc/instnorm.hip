@@ -13,10 +13,9 @@
 // ATen's reductions over the middle axes of a channels-last tensor ran at ~100 us per call (21 ms per MedFormer step).
 #include "common.hpp"
 #include "misc.hpp"
+#include "mf_tiles.hpp"      // CN_CG, CN_VPB, CS_CG, CS_VPB
 
 namespace {
-
-constexpr int CN_CG = 64, CN_VPB = 16;
 
 struct CnParams {
     const float* x; const float* dy; const float* mr; const float* gm;
@@ -111,7 +110,6 @@ __global__ __launch_bounds__(256) void cnorm_apply_kernel(CnParams p) {
 // (sample, 16-channel group: 4 channel vectors x 64 voxel lanes -- round 3; 64-channel groups left 10 blocks on the chip for 320 channels and 14
 // dependent trips per thread) does statistics, finalize and apply in ONE launch -- the three-launch path is pure launch latency there.
 // Same arithmetic: f32 partial sums per thread, fixed-order f64 combination, mean / rstd (or m1 / m2) in f32.
-constexpr int CS_CG = 16, CS_VPB = 64;
 template <int MODE>
 __global__ __launch_bounds__(256) void cnorm_small_kernel(CnParams p, float eps, float* mr_out) {
     __shared__ double red[4][2][CS_CG];
@@ -191,29 +189,40 @@ __global__ __launch_bounds__(256) void cnorm_small_kernel(CnParams p, float eps,
 
 }  // namespace
 
-int rs_cnorm_rows(long vox) {
-    long b = (vox + CN_VPB * 8 - 1) / (CN_VPB * 8);
-    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
-}
+// One launch of cnorm kernel template K<MODE> on the plan's grid; pl.sel = MODE
+#define RS_CN_LAUNCH(K, MODE, ...) hipLaunchKernelGGL(K<MODE>, dim3((unsigned)pl.bx, (unsigned)pl.by, (unsigned)pl.bz), dim3(pl.threads), 0, st, __VA_ARGS__)
 
-int rs_launch_cnorm_stats(const float* x, const float* dy, const float* mr, float* part, int N, long vox, int C, int relu, int mode, hipStream_t st) {
-    const int rows = rs_cnorm_rows(vox);
-    CnParams p = {x, dy, mr, nullptr, nullptr, part, vox, C, relu, rows};
-    dim3 grid(rows, (C + CN_CG - 1) / CN_CG, N);
-    if (mode == 0) hipLaunchKernelGGL(cnorm_stats_kernel<0>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(cnorm_stats_kernel<1>, grid, dim3(256), 0, st, p);
+int rs_launch_cnorm_stats(const float* x, const float* dy, const float* mr, float* part, int N, long vox, int C, int relu, const GluePlan& pl, hipStream_t st) {
+    CnParams p = {x, dy, mr, nullptr, nullptr, part, vox, C, relu, pl.rows};
+    switch (pl.kernel == MF_CNORM_STATS ? pl.sel : -1) {
+        case 0: RS_CN_LAUNCH(cnorm_stats_kernel, 0, p); break;
+        case 1: RS_CN_LAUNCH(cnorm_stats_kernel, 1, p); break;
+        default: return RS_ERR_UNSUPPORTED;
+    }
     return rs_check_launch();
 }
 
-int rs_launch_cnorm_apply(const float* x, const float* dy, const float* mr, const float* gm, float* out, int N, long vox, int C, int relu, int mode,
+int rs_launch_cnorm_apply(const float* x, const float* dy, const float* mr, const float* gm, float* out, int N, long vox, int C, int relu, const GluePlan& pl,
                           hipStream_t st) {
     CnParams p = {x, dy, mr, gm, out, nullptr, vox, C, relu, 0};
-    long bx = (vox + CN_VPB - 1) / CN_VPB;
-    if (bx > 2048) bx = 2048;
-    dim3 grid((unsigned)bx, (C + CN_CG - 1) / CN_CG, N);
-    if (mode == 0) hipLaunchKernelGGL(cnorm_apply_kernel<0>, grid, dim3(256), 0, st, p);
-    else if (mode == 1) hipLaunchKernelGGL(cnorm_apply_kernel<1>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(cnorm_apply_kernel<2>, grid, dim3(256), 0, st, p);
+    switch (pl.kernel == MF_CNORM_APPLY ? pl.sel : -1) {
+        case 0: RS_CN_LAUNCH(cnorm_apply_kernel, 0, p); break;
+        case 1: RS_CN_LAUNCH(cnorm_apply_kernel, 1, p); break;
+        case 2: RS_CN_LAUNCH(cnorm_apply_kernel, 2, p); break;
+        default: return RS_ERR_UNSUPPORTED;
+    }
+    return rs_check_launch();
+}
+
+// One-launch path for small volumes.  mode 0: out = norm(x) (+relu), mr_out = (mean, rstd); mode 1: out = dx from (x, dy, mr).
+int rs_launch_cnorm_small(const float* x, const float* dy, const float* mr, float* out, float* mr_out, int N, long vox, int C, int relu, float eps,
+                          const GluePlan& pl, hipStream_t st) {
+    CnParams p = {x, dy, mr, nullptr, out, nullptr, vox, C, relu, 0};
+    switch (pl.kernel == MF_CNORM_SMALL ? pl.sel : -1) {
+        case 0: RS_CN_LAUNCH(cnorm_small_kernel, 0, p, eps, mr_out); break;
+        case 1: RS_CN_LAUNCH(cnorm_small_kernel, 1, p, eps, mr_out); break;
+        default: return RS_ERR_UNSUPPORTED;
+    }
     return rs_check_launch();
 }
 
@@ -409,58 +418,31 @@ __global__ __launch_bounds__(256) void cl_planar_kernel(const float* __restrict_
 
 }  // namespace
 
-// SEBlock forward in one host call: channel means (statistics + finalize), excitation, y = x * s.  scratch: part (cnorm rows), ms (N, C, 2),
-// tab (N, C, 2) = (0, s) and hbuf (N, r) are kept by the caller for the backward pass.
-int rs_launch_se_forward(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* part, float* ms, float* tab,
-                         float* hbuf, float* y, int N, long vox, int C, int r, hipStream_t st) {
-    if (C > 8192 || r > 8192 || r < 1) return RS_ERR_UNSUPPORTED;
-    const int rows = rs_cnorm_rows(vox);
-    int rc = rs_launch_cnorm_stats(x, nullptr, nullptr, part, N, vox, C, 0, 0, st);
-    if (rc != RS_OK) return rc;
-    rc = rs_launch_stats_finalize(part, N, rows, C, (double)vox, 0.f, 1, 0, ms, st);
-    if (rc != RS_OK) return rc;
-    hipLaunchKernelGGL(se_hidden_fwd_kernel, dim3(N, (r + 15) / 16), dim3(1024), 0, st, (const float*)ms, w1, b1, hbuf, C, r);
-    hipLaunchKernelGGL(se_gate_fwd_kernel, dim3(N, (C + 63) / 64), dim3(1024), 0, st, (const float*)hbuf, w2, b2, tab, C, r);
-    rc = rs_check_launch();
-    if (rc != RS_OK) return rc;
-    return rs_launch_cnorm_apply(x, nullptr, tab, nullptr, y, N, vox, C, 0, 2, st);
-}
-
-// SEBlock backward in one host call.  ident: (N, C, 2) table of (0, 1) (the statistics kernel then yields the means of (dy, dy * x)).
-int rs_launch_se_backward(const float* x, const float* dy, const float* ident, const float* w1, const float* w2, const float* ms, const float* tab,
-                          const float* hbuf, float* part, float* gm, float* dz1buf, float* tab2, float* dx, float* dw1, float* db1, float* dw2,
-                          float* db2, int N, long vox, int C, int r, hipStream_t st) {
-    if (C > 8192 || r > 8192 || r < 1) return RS_ERR_UNSUPPORTED;
-    const int rows = rs_cnorm_rows(vox);
-    int rc = rs_launch_cnorm_stats(x, dy, ident, part, N, vox, C, 0, 1, st);
-    if (rc != RS_OK) return rc;
-    rc = rs_launch_stats_finalize(part, N, rows, C, (double)vox, 0.f, 1, 0, gm, st);
-    if (rc != RS_OK) return rc;
-    hipLaunchKernelGGL(se_excite_bwd_hidden_kernel, dim3(N, (r + 31) / 32), dim3(1024), (size_t)(C + 32 * 33) * sizeof(float), st, (const float*)gm, tab,
-                       hbuf, w2, (float)vox, dz1buf, C, r);
-    const long total = (long)C * r;
-    hipLaunchKernelGGL(se_excite_wgrad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)gm, tab, hbuf, ms,
-                       (const float*)dz1buf, (float)vox, N, C, r, dw1, db1, dw2, db2);
-    hipLaunchKernelGGL(se_dm_kernel, dim3(N, (C + 31) / 32), dim3(1024), 0, st, (const float*)dz1buf, w1, tab, (float)vox, tab2, C, r);
-    rc = rs_check_launch();
-    if (rc != RS_OK) return rc;
-    return rs_launch_cnorm_apply(dy, nullptr, tab2, nullptr, dx, N, vox, C, 0, 2, st);
-}
-
-int rs_launch_cl_planar(const float* src, float* dst, int N, long vox, int C, int K, int dir, hipStream_t st) {
-    if (C > 64 || (C & 3) || K > C || K < 1) return RS_ERR_UNSUPPORTED;
-    const long bx = (vox + 127) / 128;
-    if (bx > 0x7FFFFFFFL) return RS_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(cl_planar_kernel, dim3((unsigned)bx, N), dim3(256), 0, st, src, dst, vox, C, K, dir);
+// SEBlock's excitation (between the channel statistics and the affine apply, which api.hip launches around it).  Forward: hbuf (N, r) hidden
+// units, tab (N, C, 2) = (0, s); both are kept by the caller for the backward pass.
+int rs_launch_se_excite(const float* ms, const float* w1, const float* b1, const float* w2, const float* b2, float* hbuf, float* tab, int C, int r,
+                        const GluePlan& hidden, const GluePlan& gate, hipStream_t st) {
+    if (hidden.kernel != MF_SE_HIDDEN_FWD || gate.kernel != MF_SE_GATE_FWD) return RS_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(se_hidden_fwd_kernel, dim3(hidden.bx, hidden.by), dim3(hidden.threads), 0, st, ms, w1, b1, hbuf, C, r);
+    hipLaunchKernelGGL(se_gate_fwd_kernel, dim3(gate.bx, gate.by), dim3(gate.threads), 0, st, (const float*)hbuf, w2, b2, tab, C, r);
     return rs_check_launch();
 }
 
-// One-launch path for small volumes.  mode 0: out = norm(x) (+relu), mr_out = (mean, rstd); mode 1: out = dx from (x, dy, mr).
-int rs_launch_cnorm_small(const float* x, const float* dy, const float* mr, float* out, float* mr_out, int N, long vox, int C, int relu, float eps,
-                          int mode, hipStream_t st) {
-    CnParams p = {x, dy, mr, nullptr, out, nullptr, vox, C, relu, 0};
-    dim3 grid((C + 15) / 16, N);
-    if (mode == 0) hipLaunchKernelGGL(cnorm_small_kernel<0>, grid, dim3(256), 0, st, p, eps, mr_out);
-    else hipLaunchKernelGGL(cnorm_small_kernel<1>, grid, dim3(256), 0, st, p, eps, mr_out);
+// Backward: gm (N, C, 2) the means of (dy, dy * x); writes the weight gradients and tab2, the affine map of dy -> dx.
+int rs_launch_se_excite_bwd(const float* gm, const float* tab, const float* hbuf, const float* ms, const float* w1, const float* w2, float* dz1buf, float* tab2,
+                            float* dw1, float* db1, float* dw2, float* db2, int N, long vox, int C, int r, const GluePlan& hidden, const GluePlan& wgrad,
+                            const GluePlan& dm, hipStream_t st) {
+    if (hidden.kernel != MF_SE_BWD_HIDDEN || wgrad.kernel != MF_SE_WGRAD || dm.kernel != MF_SE_DM) return RS_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(se_excite_bwd_hidden_kernel, dim3(hidden.bx, hidden.by), dim3(hidden.threads), (size_t)hidden.lds, st, gm, tab, hbuf, w2, (float)vox,
+                       dz1buf, C, r);
+    hipLaunchKernelGGL(se_excite_wgrad_kernel, dim3(wgrad.bx), dim3(wgrad.threads), 0, st, gm, tab, hbuf, ms, (const float*)dz1buf, (float)vox, N, C, r, dw1,
+                       db1, dw2, db2);
+    hipLaunchKernelGGL(se_dm_kernel, dim3(dm.bx, dm.by), dim3(dm.threads), 0, st, (const float*)dz1buf, w1, tab, (float)vox, tab2, C, r);
+    return rs_check_launch();
+}
+
+int rs_launch_cl_planar(const float* src, float* dst, int N, long vox, int C, int K, int dir, const GluePlan& pl, hipStream_t st) {
+    if (pl.kernel != MF_CL_PLANAR) return RS_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(cl_planar_kernel, dim3((unsigned)pl.bx, pl.by), dim3(pl.threads), 0, st, src, dst, vox, C, K, dir);
     return rs_check_launch();
 }

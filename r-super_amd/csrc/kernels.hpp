@@ -126,12 +126,11 @@ int rs_launch_wgrad2(const WgradParams& p, int mt, hipStream_t st);
 int rs_wgrad_s2_splits(int dtype, int Ca, int Mtot, int N, int D, int H, int W);
 int rs_launch_wgrad_s2(const WgradParams& p, int dtype, hipStream_t st);
 
-// 1x1x1 convolution / linear layer as an MFMA GEMM on f32 channels-last rows (pointwise.hip); packed = workspace of rs_pw_packed_bytes
-size_t rs_pw_packed_bytes(int N, int K, int dtype);
-int rs_launch_pointwise(int dtype, int mode, const float* x, int ldx, const float* w, const float* bias, const float* res, int ldr,
-                        float* y, int ldy, int R, int K, int N, void* packed, hipStream_t st);
-// weight (+ bias) gradient of the same layer: dW = dy^T x, db = column sums of dy; part = workspace of S * (N*K + N) floats, S = rs_pw_wgrad_splits
-int rs_pw_wgrad_splits(int R, int N, int K);
-int rs_launch_pointwise_pack_batch(int dtype, const long long* table, int n, long total_items, void* arena, hipStream_t st);
-int rs_launch_pointwise_wgrad(int dtype, const float* dy, int ldy, const float* x, int ldx, int R, int N, int K, float* part, int S,
-                              float* dw, float* db, hipStream_t st);
+// 1x1x1 convolution / linear layer as an MFMA GEMM on f32 channels-last rows (pointwise.hip) and the weight (+ bias) gradient of the same layer,
+// dW = dy^T x, db = column sums of dy.  The plans (GluePlan, misc.hpp) and the sizes of `packed` and `part` are mf_plan.hpp's.
+struct GluePlan;
+int rs_launch_pointwise(int mode, const float* x, int ldx, const float* w, const float* bias, const float* res, int ldr, float* y, int ldy, int R, int K,
+                        int N, void* packed, const GluePlan& pack, const GluePlan& pl, hipStream_t st);
+int rs_launch_pointwise_pack_batch(const long long* table, int n, long total_items, void* arena, const GluePlan& pl, hipStream_t st);
+int rs_launch_pointwise_wgrad(const float* dy, int ldy, const float* x, int ldx, int R, int N, int K, float* part, float* dw, float* db, const GluePlan& pl,
+                              const GluePlan& reduce, hipStream_t st);

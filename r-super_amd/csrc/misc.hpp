@@ -55,24 +55,11 @@ struct HeadParams {
     int N, vox, C, K;
 };
 
-int rs_cnorm_rows(long vox);
-int rs_launch_cnorm_small(const float* x, const float* dy, const float* mr, float* out, float* mr_out, int N, long vox, int C, int relu, float eps, int mode, hipStream_t st);
-int rs_launch_cnorm_stats(const float* x, const float* dy, const float* mr, float* part, int N, long vox, int C, int relu, int mode, hipStream_t st);
-int rs_launch_cnorm_apply(const float* x, const float* dy, const float* mr, const float* gm, float* out, int N, long vox, int C, int relu, int mode, hipStream_t st);
 int rs_battn_supported(int T, int dh, int heads);
 int rs_battn_chunks(int L, int heads);
 int rs_launch_battn(const float* fqv, const float* mqv, float* fout, float* mout, float* lse, const float* dfo, const float* dmo,
                     float* dfqv, float* dmqv, float* part, float* pms, int B, int L, int T, int heads, int dh, float scale, int bwd,
                     hipStream_t st);
-int rs_launch_se_forward(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* part, float* ms, float* tab,
-                         float* hbuf, float* y, int N, long vox, int C, int r, hipStream_t st);
-int rs_launch_se_backward(const float* x, const float* dy, const float* ident, const float* w1, const float* w2, const float* ms, const float* tab,
-                          const float* hbuf, float* part, float* gm, float* dz1buf, float* tab2, float* dx, float* dw1, float* db1, float* dw2,
-                          float* db2, int N, long vox, int C, int r, hipStream_t st);
-int rs_launch_cl_planar(const float* src, float* dst, int N, long vox, int C, int K, int dir, hipStream_t st);
-int rs_depthwise_rows(long vox);
-int rs_launch_depthwise(const float* x, const float* w, float* y, int N, int D, int H, int W, int C, int flip, hipStream_t st);
-int rs_launch_depthwise_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int D, int H, int W, int C, hipStream_t st);
 int rs_launch_stats_finalize(const float* part, int N, int nblk, int C, double cnt, float eps, int mode, int split, float* out, hipStream_t st);
 int rs_elem_blocks(size_t items);
 int rs_glue_variant(int v);      // 1: tuned bandwidth-bound kernels (default), 0: the ones they replaced; other values query (defined in glue_plan.hpp)
@@ -103,3 +90,36 @@ int rs_launch_upsample(const UpParams& p, const GluePlan& pl, hipStream_t st, co
                        const float* gm = nullptr);
 int rs_launch_stem(const StemParams& p, int dtype, int wgrad, hipStream_t st);
 int rs_launch_head(const HeadParams& p, int dtype, int which, hipStream_t st);
+
+// One launch of the MedFormer-stage family (pointwise.hip, depthwise.hip, instnorm.hip), as mf_plan.hpp decides it: a GluePlan whose `kernel` is an
+// MfKernel.  The launchers switch over `kernel` / `sel` and look at no shape, limit or environment variable themselves; rsuper_mf_plan hands the same
+// fields to tests.  sel: NF of pw_gemm (1, 2, 4), WNW of pw_wgrad (1, 2, 4), MODE of the cnorm kernels.  arg: KSPLIT of pw_gemm, rows_per of
+// pw_wgrad, dsegs of depthwise_lds.  rows: rows of `part` (cnorm statistics, depthwise weight gradient), slabs of the pw_wgrad workspace.
+enum MfOp {                      // one per launch; shape of rsuper_mf_plan in brackets
+    MF_OP_PW_PACK, MF_OP_PW_PACK_BATCH, MF_OP_PW,                      // [K, N], [items], [R, K, N]
+    MF_OP_PW_WGRAD, MF_OP_PW_WGRAD_REDUCE,                             // [R, N, K]
+    MF_OP_DW, MF_OP_DW_WGRAD, MF_OP_DW_WGRAD_REDUCE,                   // [N, D, H, W, C]
+    MF_OP_CNORM, MF_OP_CNORM_STATS, MF_OP_CNORM_APPLY,                 // [N, vox, C, mode]; MF_OP_CNORM: the first launch of rsuper_cnorm_forward (mode 0) / _backward (1)
+    MF_OP_SE_HIDDEN, MF_OP_SE_GATE, MF_OP_SE_BWD_HIDDEN, MF_OP_SE_WGRAD, MF_OP_SE_DM,      // [N, C, r]
+    MF_OP_CL_PLANAR,                                                   // [N, vox, C, K]
+    MF_OP_COUNT
+};
+enum MfKernel {                  // one value per __global__ of the family; MF_NONE: no launch (a refused shape answers RS_ERR_UNSUPPORTED)
+    MF_NONE = -1, MF_PW_PACK, MF_PW_PACK_BATCH, MF_PW_GEMM, MF_PW_WGRAD, MF_PW_WGRAD_REDUCE, MF_DW_FWD, MF_DW_LDS, MF_DW_WGRAD, MF_DW_WGRAD_REDUCE,
+    MF_CNORM_STATS, MF_CNORM_APPLY, MF_CNORM_SMALL, MF_SE_HIDDEN_FWD, MF_SE_GATE_FWD, MF_SE_BWD_HIDDEN, MF_SE_WGRAD, MF_SE_DM, MF_CL_PLANAR
+};
+int rs_launch_cnorm_small(const float* x, const float* dy, const float* mr, float* out, float* mr_out, int N, long vox, int C, int relu, float eps, const GluePlan& pl,
+                          hipStream_t st);
+int rs_launch_cnorm_stats(const float* x, const float* dy, const float* mr, float* part, int N, long vox, int C, int relu, const GluePlan& pl, hipStream_t st);
+int rs_launch_cnorm_apply(const float* x, const float* dy, const float* mr, const float* gm, float* out, int N, long vox, int C, int relu, const GluePlan& pl,
+                          hipStream_t st);
+// the excitation between the channel statistics and the affine apply of SEBlock (api.hip strings the five launches of a direction together)
+int rs_launch_se_excite(const float* ms, const float* w1, const float* b1, const float* w2, const float* b2, float* hbuf, float* tab, int C, int r,
+                        const GluePlan& hidden, const GluePlan& gate, hipStream_t st);
+int rs_launch_se_excite_bwd(const float* gm, const float* tab, const float* hbuf, const float* ms, const float* w1, const float* w2, float* dz1buf, float* tab2,
+                            float* dw1, float* db1, float* dw2, float* db2, int N, long vox, int C, int r, const GluePlan& hidden, const GluePlan& wgrad,
+                            const GluePlan& dm, hipStream_t st);
+int rs_launch_cl_planar(const float* src, float* dst, int N, long vox, int C, int K, int dir, const GluePlan& pl, hipStream_t st);
+int rs_launch_depthwise(const float* x, const float* w, float* y, int N, int D, int H, int W, int C, int flip, const GluePlan& pl, hipStream_t st);
+int rs_launch_depthwise_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int D, int H, int W, int C, const GluePlan& pl,
+                              const GluePlan& reduce, hipStream_t st);

@@ -20,6 +20,8 @@
 // in the f32 parity mode; storage stays fp32 either way (the attention stages' activation dtype).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "misc.hpp"
+#include "mf_tiles.hpp"
 
 namespace {
 
@@ -192,26 +194,6 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwParams p) {
     }
 }
 
-template <typename CT>
-int launch_pw(const PwParams& p, hipStream_t st) {
-    const int nf = p.ntiles >= 4 ? 4 : p.ntiles >= 2 ? 2 : 1;
-    const unsigned gy = (unsigned)((p.ntiles + nf - 1) / nf);
-    // split the reduction over the waves when whole-K blocks of 128 rows would cover less than half of the CUs
-    const bool ksplit = p.ksteps >= 8 && (long)((p.R + 127) / 128) * gy < 128;   // measured: 216 whole-K blocks beat 864 split ones (26 vs 37 us), 54 lose (37 vs 17 us)
-    dim3 grid((unsigned)((p.R + (ksplit ? 31 : 127)) / (ksplit ? 32 : 128)), gy), block(256);
-    if (ksplit) {
-        if (nf == 4) hipLaunchKernelGGL((pw_gemm_kernel<CT, 4, true>), grid, block, 0, st, p);
-        else if (nf == 2) hipLaunchKernelGGL((pw_gemm_kernel<CT, 2, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((pw_gemm_kernel<CT, 1, true>), grid, block, 0, st, p);
-    } else {
-        if (nf == 4) hipLaunchKernelGGL((pw_gemm_kernel<CT, 4, false>), grid, block, 0, st, p);
-        else if (nf == 2) hipLaunchKernelGGL((pw_gemm_kernel<CT, 2, false>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((pw_gemm_kernel<CT, 1, false>), grid, block, 0, st, p);
-    }
-    return rs_check_launch();
-}
-
-
 // ------------------------------------------------------------------------------------------------ weight (+ bias) gradient
 //   dW[n][k] = sum_r dy[r][n] * x[r][k],   db[n] = sum_r dy[r][n]            (dy: [R][ldy] f32, x: [R][ldx] f32, dW: (N, K) as the state_dict)
 // The reduction runs over the SLOW memory axis of both operands, so a lane's fragment (KP consecutive reduction steps of one channel) is KP
@@ -343,70 +325,59 @@ __global__ __launch_bounds__(256) void pw_wgrad_reduce_kernel(const float* __res
     else if (db) *(float4*)(db + (e - NK)) = s;
 }
 
-template <typename CT>
-int launch_pw_wgrad(PwWgParams p, int S, float* dw, float* db, hipStream_t st) {
-    p.out_w = S == 1 ? dw : nullptr; p.out_b = S == 1 ? db : nullptr;
-    const int wnw = p.N <= 64 ? 1 : p.K <= 64 ? 4 : 2;
-    dim3 grid((unsigned)((p.N + wnw * 64 - 1) / (wnw * 64)), (unsigned)((p.K + (4 / wnw) * 64 - 1) / ((4 / wnw) * 64)), (unsigned)S), block(256);
-    if (wnw == 1) hipLaunchKernelGGL((pw_wgrad_kernel<CT, 1>), grid, block, 0, st, p);
-    else if (wnw == 4) hipLaunchKernelGGL((pw_wgrad_kernel<CT, 4>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((pw_wgrad_kernel<CT, 2>), grid, block, 0, st, p);
-    const long NK = (long)p.N * p.K, E = NK + p.N;
-    if (S > 1) hipLaunchKernelGGL(pw_wgrad_reduce_kernel, dim3((unsigned)((E / 4 + 255) / 256)), dim3(256), 0, st, (const float*)p.part, S, E, NK, dw, db);
-    return rs_check_launch();
-}
-
 }  // namespace
 
-size_t rs_pw_packed_bytes(int N, int K, int dtype) {
-    const int KS = dtype == RS_F32 ? 8 : 16;
-    return (size_t)((K + KS - 1) / KS) * ((N + 31) / 32) * 64 * 16;
-}
+// One launch of kernel template K<compute type, ...> for the plan's compute type, on the plan's grid
+#define RS_PW_LAUNCH(K, ...)                                                                                                          \
+    do {                                                                                                                              \
+        const dim3 grid_((unsigned)pl.bx, (unsigned)pl.by, (unsigned)pl.bz);                                                         \
+        if (pl.dtype == RS_F32) hipLaunchKernelGGL((K<float, __VA_ARGS__>), grid_, dim3(pl.threads), 0, st, p);          \
+        else hipLaunchKernelGGL((K<bf16_t, __VA_ARGS__>), grid_, dim3(pl.threads), 0, st, p);                             \
+    } while (0)
 
-// mode 0: y = x W^T (+ bias), W (N, K);  mode 1: y = x W, W (K, N) (the data gradient of mode 0 with x := dy)
-int rs_launch_pointwise(int dtype, int mode, const float* x, int ldx, const float* w, const float* bias, const float* res, int ldr,
-                        float* y, int ldy, int R, int K, int N, void* packed, hipStream_t st) {
-    const int KS = dtype == RS_F32 ? 8 : 16;
+// mode 0: y = x W^T (+ bias), W (N, K);  mode 1: y = x W, W (K, N) (the data gradient of mode 0 with x := dy).  w == nullptr: `packed` holds the
+// fragments already and `pack` is not launched.
+int rs_launch_pointwise(int mode, const float* x, int ldx, const float* w, const float* bias, const float* res, int ldr, float* y, int ldy, int R, int K,
+                        int N, void* packed, const GluePlan& pack, const GluePlan& pl, hipStream_t st) {
     PwParams p;
     p.x = x; p.ldx = ldx; p.wp = packed; p.bias = bias; p.res = res; p.ldr = ldr; p.y = y; p.ldy = ldy; p.R = R; p.K = K; p.N = N;
-    p.ntiles = (N + 31) / 32; p.ksteps = (K + KS - 1) / KS;
-    const int items = p.ksteps * p.ntiles * 64;
+    p.ntiles = pw_ntiles(N); p.ksteps = pw_ksteps(K, pl.dtype == RS_F32);
     const int rows = mode == 0 ? N : K, cols = mode == 0 ? K : N;
-    if (dtype == RS_F32) {
-        if (w) hipLaunchKernelGGL(pw_pack_kernel<float>, dim3((items + 255) / 256), dim3(256), 0, st, w, rows, cols, mode, p.ntiles, p.ksteps, (float*)packed);
-        return launch_pw<float>(p, st);
+    if (w && pack.dtype == RS_F32) hipLaunchKernelGGL(pw_pack_kernel<float>, dim3(pack.bx), dim3(pack.threads), 0, st, w, rows, cols, mode, p.ntiles, p.ksteps, (float*)packed);
+    else if (w) hipLaunchKernelGGL(pw_pack_kernel<bf16_t>, dim3(pack.bx), dim3(pack.threads), 0, st, w, rows, cols, mode, p.ntiles, p.ksteps, (bf16_t*)packed);
+    switch (pl.sel * 2 + pl.arg) {                           // NF, KSPLIT
+        case 9: RS_PW_LAUNCH(pw_gemm_kernel, 4, true); break;
+        case 8: RS_PW_LAUNCH(pw_gemm_kernel, 4, false); break;
+        case 5: RS_PW_LAUNCH(pw_gemm_kernel, 2, true); break;
+        case 4: RS_PW_LAUNCH(pw_gemm_kernel, 2, false); break;
+        case 3: RS_PW_LAUNCH(pw_gemm_kernel, 1, true); break;
+        case 2: RS_PW_LAUNCH(pw_gemm_kernel, 1, false); break;
+        default: return RS_ERR_UNSUPPORTED;
     }
-    if (w) hipLaunchKernelGGL(pw_pack_kernel<bf16_t>, dim3((items + 255) / 256), dim3(256), 0, st, w, rows, cols, mode, p.ntiles, p.ksteps, (bf16_t*)packed);
-    return launch_pw<bf16_t>(p, st);
-}
-
-int rs_launch_pointwise_pack_batch(int dtype, const long long* table, int n, long total_items, void* arena, hipStream_t st) {
-    const dim3 grid((unsigned)((total_items + 255) / 256)), block(256);
-    if (dtype == RS_F32) hipLaunchKernelGGL(pw_pack_batch_kernel<float>, grid, block, 0, st, table, n, total_items, (char*)arena);
-    else hipLaunchKernelGGL(pw_pack_batch_kernel<bf16_t>, grid, block, 0, st, table, n, total_items, (char*)arena);
     return rs_check_launch();
 }
 
-// slabs of the row axis for the weight gradient: about one resident block per CU (more slabs = more partial traffic for the reduce), at least 64 rows per slab, whole MFMA steps per slab
-int rs_pw_wgrad_splits(int R, int N, int K) {
-    const int wnw = N <= 64 ? 1 : K <= 64 ? 4 : 2;
-    const int tiles = ((N + wnw * 64 - 1) / (wnw * 64)) * ((K + (4 / wnw) * 64 - 1) / ((4 / wnw) * 64));
-    static const int target = getenv("RSUPER_PW_WG_TARGET") ? atoi(getenv("RSUPER_PW_WG_TARGET")) : 256;   // blocks per launch (measured: 128 / 256 / 512 / 1024 -> MedFormer step 28.6 / 28.5 / 28.9 / 29.4 ms)
-    static const int direct = getenv("RSUPER_PW_WG_DIRECT") ? atoi(getenv("RSUPER_PW_WG_DIRECT")) : 0;   // rows up to which ONE slab is forced (a single slab writes dW itself, no reduce launch): 768 measured no faster
-                                                                                                      // than 7 slabs + reduce at 432 rows (MedFormer 27.2 vs 27.0 ms); a naturally single slab (<= 64 rows) always writes directly
-    if (R <= direct) return 1;
-    int s = target / tiles;
-    if (s > (R + 63) / 64) s = (R + 63) / 64;
-    if (s < 1) s = 1;
-    const int rows_per = (((R + s - 1) / s) + 15) / 16 * 16;                      // as the launcher cuts them: no slab without rows
-    return (R + rows_per - 1) / rows_per;
+int rs_launch_pointwise_pack_batch(const long long* table, int n, long total_items, void* arena, const GluePlan& pl, hipStream_t st) {
+    if (pl.dtype == RS_F32) hipLaunchKernelGGL(pw_pack_batch_kernel<float>, dim3(pl.bx), dim3(pl.threads), 0, st, table, n, total_items, (char*)arena);
+    else hipLaunchKernelGGL(pw_pack_batch_kernel<bf16_t>, dim3(pl.bx), dim3(pl.threads), 0, st, table, n, total_items, (char*)arena);
+    return rs_check_launch();
 }
 
-int rs_launch_pointwise_wgrad(int dtype, const float* dy, int ldy, const float* x, int ldx, int R, int N, int K, float* part, int S,
-                              float* dw, float* db, hipStream_t st) {
+// part: pl.rows slabs of N*K + N floats; one slab writes dW / db itself and `reduce` names no launch
+int rs_launch_pointwise_wgrad(const float* dy, int ldy, const float* x, int ldx, int R, int N, int K, float* part, float* dw, float* db, const GluePlan& pl,
+                              const GluePlan& reduce, hipStream_t st) {
     PwWgParams p;
     p.dy = dy; p.ldy = ldy; p.x = x; p.ldx = ldx; p.part = part; p.R = R; p.N = N; p.K = K; p.bias = db != nullptr;
-    p.rows_per = (((R + S - 1) / S) + 15) / 16 * 16;
-    // (a slab past the last row still writes its -- zero -- partial: any S is valid, rs_pw_wgrad_splits just avoids empty ones)
-    return dtype == RS_F32 ? launch_pw_wgrad<float>(p, S, dw, db, st) : launch_pw_wgrad<bf16_t>(p, S, dw, db, st);
+    p.rows_per = pl.arg;
+    const bool direct = reduce.kernel == MF_NONE;
+    p.out_w = direct ? dw : nullptr; p.out_b = direct ? db : nullptr;
+    switch (pl.sel) {                                        // WNW
+        case 1: RS_PW_LAUNCH(pw_wgrad_kernel, 1); break;
+        case 4: RS_PW_LAUNCH(pw_wgrad_kernel, 4); break;
+        case 2: RS_PW_LAUNCH(pw_wgrad_kernel, 2); break;
+        default: return RS_ERR_UNSUPPORTED;
+    }
+    const long NK = (long)N * K;
+    if (!direct) hipLaunchKernelGGL(pw_wgrad_reduce_kernel, dim3(reduce.bx), dim3(reduce.threads), 0, st, (const float*)part, pl.rows, NK + N, NK, dw, db);
+    return rs_check_launch();
 }

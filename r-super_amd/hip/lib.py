@@ -57,6 +57,7 @@ _SIGS = {
     'rsuper_glue_variant': (c_int, [c_int]),
     'rsuper_stat_rows': (c_int, [c_int, c_long]),
     'rsuper_glue_plan': (c_int, [c_int, c_int, P, c_int, c_int, P]),
+    'rsuper_mf_plan': (c_int, [c_int, c_int, P, P]),
     'rsuper_in_bwd_finalize': (c_int, [c_int, P, c_int, P, c_int, P, P, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_fwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'rsuper_maxpool2_bwd': (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
@@ -83,6 +84,7 @@ _SIGS = {
     'rsuper_plane_sums_reduce': (c_int, [P, c_int, c_int, P, P]),
     'rsuper_plane_partials_bwd2': (c_int, [P, c_size_t, P, P, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_size_t, P]),
     'rsuper_cnorm_rows': (c_int, [c_long]),
+    'rsuper_cnorm_part_rows': (c_int, [c_long]),
     'rsuper_cnorm_small': (c_int, [P, P, P, P, P, c_int, c_long, c_int, c_int, c_float, c_int, P]),
     'rsuper_cnorm_forward': (c_int, [P, P, P, P, c_int, c_long, c_int, c_int, c_float, P]),
     'rsuper_cnorm_backward': (c_int, [P, P, P, P, P, P, c_int, c_long, c_int, c_int, P]),
@@ -198,6 +200,15 @@ GLUE_IN_BWD, GLUE_POOL_FWD, GLUE_POOL_BWD, GLUE_SUB_FWD, GLUE_SUB_BWD, GLUE_UP_F
 GLUE_KERNELS = ('in_bwd_finalize_kernel', 'in_bwd_finalize2_kernel', 'maxpool_fwd_kernel', 'maxpool_fwd2_kernel', 'maxpool_bwd_kernel',
                 'subsample_fwd_kernel', 'subsample_bwd_kernel', 'upsample_fwd_kernel', 'upsample_fwd2_kernel', 'upsample_fwd3_kernel',
                 'upsample_bwd_kernel', 'upsample_bwd2_kernel', 'upsample_bwd4_kernel')
+# `op` of rsuper_mf_plan, one per launch of csrc/pointwise.hip, depthwise.hip and instnorm.hip (shapes: include/rsuper_hip.h)
+(MF_PW_PACK, MF_PW_PACK_BATCH, MF_PW, MF_PW_WGRAD, MF_PW_WGRAD_REDUCE, MF_DW, MF_DW_WGRAD, MF_DW_WGRAD_REDUCE, MF_CNORM, MF_CNORM_STATS, MF_CNORM_APPLY,
+ MF_SE_HIDDEN, MF_SE_GATE, MF_SE_BWD_HIDDEN, MF_SE_WGRAD, MF_SE_DM, MF_CL_PLANAR) = range(17)
+# out[0] of rsuper_mf_plan: the __global__ that runs; out[1..9] are MF_PLAN_FIELDS[1:]
+MF_KERNELS = ('pw_pack_kernel', 'pw_pack_batch_kernel', 'pw_gemm_kernel', 'pw_wgrad_kernel', 'pw_wgrad_reduce_kernel', 'depthwise_fwd_kernel',
+              'depthwise_lds_kernel', 'depthwise_wgrad_kernel', 'depthwise_wgrad_reduce_kernel', 'cnorm_stats_kernel', 'cnorm_apply_kernel',
+              'cnorm_small_kernel', 'se_hidden_fwd_kernel', 'se_gate_fwd_kernel', 'se_excite_bwd_hidden_kernel', 'se_excite_wgrad_kernel', 'se_dm_kernel',
+              'cl_planar_kernel')
+MF_PLAN_FIELDS = ('kernel', 'sel', 'bx', 'by', 'bz', 'threads', 'lds', 'rows', 'arg', 'ws')
 
 ERR = {1: 'RSUPER_ERR_ARG', 2: 'RSUPER_ERR_LAUNCH', 3: 'RSUPER_ERR_UNSUPPORTED', 4: 'RSUPER_ERR_NO_DEVICE'}
 

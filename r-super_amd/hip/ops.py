@@ -1240,9 +1240,6 @@ def channel_stats(x, eps):
     return mr
 
 
-CNORM_SMALL_VOX = int(os.environ.get('RSUPER_CNORM_SMALL_VOX', '512'))
-
-
 class ChannelNormFn(torch.autograd.Function):
     """InstanceNorm3d(affine=False, eps) [+ ReLU] of a channels-last fp32 tensor (N, D, H, W, C), forward and backward on
     csrc/instnorm.hip (per-block partial sums + the deterministic f64 finalize shared with the conv epilogues)."""
@@ -1257,15 +1254,9 @@ class ChannelNormFn(torch.autograd.Function):
         vox = x.shape[1] * x.shape[2] * x.shape[3]
         mr = torch.empty((N, C, 2), device=x.device, dtype=torch.float32)
         y = torch.empty_like(x)
-        st = _stream()
         ctx.relu = bool(relu)
-        if vox <= CNORM_SMALL_VOX:               # low-resolution stages / semantic maps: one launch
-            _l.check(_L().rsuper_cnorm_small(_ptr(x), None, None, _ptr(y), _ptr(mr), N, vox, C, int(relu), float(eps), 0, st), 'cnorm_small')
-            ctx.save_for_backward(x, mr)
-            return y
-        rows = _L().rsuper_cnorm_rows(vox)
-        part = torch.empty((N, rows, C, 2), device=x.device, dtype=torch.float32)
-        _l.check(_L().rsuper_cnorm_forward(_ptr(x), _ptr(part), _ptr(mr), _ptr(y), N, vox, C, int(relu), float(eps), st), 'cnorm_forward')
+        part = _cnorm_part(x, N, vox, C)
+        _l.check(_L().rsuper_cnorm_forward(_ptr(x), _ptr(part), _ptr(mr), _ptr(y), N, vox, C, int(relu), float(eps), _stream()), 'cnorm_forward')
         ctx.save_for_backward(x, mr)
         return y
 
@@ -1275,17 +1266,17 @@ class ChannelNormFn(torch.autograd.Function):
         dy = dy.contiguous()
         N, C = x.shape[0], x.shape[-1]
         vox = x.shape[1] * x.shape[2] * x.shape[3]
-        if vox <= CNORM_SMALL_VOX:
-            dx = torch.empty_like(x)
-            _l.check(_L().rsuper_cnorm_small(_ptr(x), _ptr(dy), _ptr(mr), _ptr(dx), None, N, vox, C, int(ctx.relu), 0.0, 1, _stream()), 'cnorm_small_bwd')
-            return dx, None, None
-        rows = _L().rsuper_cnorm_rows(vox)
-        part = torch.empty((N, rows, C, 2), device=x.device, dtype=torch.float32)
-        gm = torch.empty((N, C, 2), device=x.device, dtype=torch.float32)
+        part = _cnorm_part(x, N, vox, C)
+        gm = torch.empty((N, C, 2), device=x.device, dtype=torch.float32) if part is not None else None
         dx = torch.empty_like(x)
-        st = _stream()
-        _l.check(_L().rsuper_cnorm_backward(_ptr(x), _ptr(dy), _ptr(mr), _ptr(part), _ptr(gm), _ptr(dx), N, vox, C, int(ctx.relu), st), 'cnorm_backward')
+        _l.check(_L().rsuper_cnorm_backward(_ptr(x), _ptr(dy), _ptr(mr), _ptr(part), _ptr(gm), _ptr(dx), N, vox, C, int(ctx.relu), _stream()), 'cnorm_backward')
         return dx, None, None
+
+
+def _cnorm_part(x, N, vox, C):
+    """Partial statistics rows of rsuper_cnorm_forward / _backward; None where the plan (csrc/mf_plan.hpp) gives the norm one launch, which has none."""
+    rows = _L().rsuper_cnorm_part_rows(vox)
+    return torch.empty((N, rows, C, 2), device=x.device, dtype=torch.float32) if rows else None
 
 
 class DepthwiseConvFn(torch.autograd.Function):
@@ -1469,8 +1460,10 @@ def pointwise_wgrad(dy2, x2, want_bias, compute):
     assert dy2.stride(1) == 1 and x2.stride(1) == 1 and dy2.stride(0) % 4 == 0 and x2.stride(0) % 4 == 0      # column slices of wider matrices are fine
     R, N = dy2.shape
     K = x2.shape[1]
-    S = _L().rsuper_pointwise_wgrad_splits(R, N, K)
-    ws = torch.empty((S * (N * K + N),), device=dy2.device, dtype=torch.float32)
+    plan = (ctypes.c_int * 10)()
+    _l.check(_L().rsuper_mf_plan(_l.MF_PW_WGRAD, _DT[compute], (ctypes.c_int * 3)(R, N, K), plan), 'mf_plan')
+    S = plan[7]                                              # slabs of the rows; plan[9]: their floats (lib.MF_PLAN_FIELDS)
+    ws = torch.empty((plan[9],), device=dy2.device, dtype=torch.float32)
     dw = torch.empty((N, K), device=dy2.device, dtype=torch.float32)
     db = torch.empty((N,), device=dy2.device, dtype=torch.float32) if want_bias else None
     _l.check(_L().rsuper_pointwise_wgrad(_DT[compute], _ptr(dy2), dy2.stride(0), _ptr(x2), x2.stride(0), R, N, K, _ptr(ws), S, _ptr(dw), _ptr(db) if want_bias else None,
