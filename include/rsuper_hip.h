@@ -877,6 +877,31 @@ int rsuper_adamw_ema_step_dyn(int n, void* const* host_p, void* const* host_g, v
                               void* const* host_ema, const size_t* host_numel, float beta1, float beta2, float eps, float weight_decay,
                               float max_norm, const double* total_sq, const float* dyn, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DEFLATE on the device -- the np.savez_compressed of uint8 masks (baselines/pseudo_labels/pseudo_label_report_refinement.py:153,
+ * to_npz.py:63, and the .npz files this package's predict_abdomenatlas writes), a zlib pass on one host thread.  csrc/deflate.hip.
+ * ------------------------------------------------------------------------------------------------ */
+/* Every plane becomes one raw DEFLATE stream (RFC 1951) that zlib inflates with wbits = -15: one byte-aligned fragment per chunk of
+ * rsuper_deflate_chunk_bytes() input bytes -- a Huffman block with the caller's code table closed by an empty stored block, or a stored block when that is
+ * shorter -- and the closing block 01 00 00 FF FF.  Tokens are literals and matches of 3..258 bytes at distance 1 (a run) or `pitch` (the row above);
+ * the greedy rule is written down at the top of csrc/deflate.hip and restated in tests/deflate_ref.py.  Integer arithmetic only: the bytes are a function
+ * of the input.
+ * Host functions: the largest stream of an n-byte plane (<= n + n / 1024 + 64), the workspace of a call, the chunk and the segment (the bytes one lane
+ * parses; a match never crosses a segment boundary). */
+size_t rsuper_deflate_bound(size_t n);
+size_t rsuper_deflate_workspace_bytes(int planes, size_t n);
+int rsuper_deflate_chunk_bytes(void);
+int rsuper_deflate_segment_bytes(void);
+/* src: planes byte planes of n bytes (0 <= n < 2^32), plane p at src + p * plane_stride (any alignment, stride >= n), 1 <= planes <= 65535.
+ * pitch: 0 (runs only) or the row length 1..32768; a larger one -> RSUPER_ERR_ARG.
+ * table: device, 316 words, (bits << 24) | bit-reversed code for the 286 literal/length symbols and then the 30 distance symbols; header: device words
+ * holding the header_bits (3..4096) bits that open a block, least significant bit first: BFINAL = 0, BTYPE and, for BTYPE 10, the code lengths.
+ * out: device, planes * rsuper_deflate_bound(n) bytes; the streams lie back to back in plane order, stream p at out + offsets[p], sizes[p] bytes long;
+ * crcs[p] = CRC-32 of plane p.  offsets, sizes, crcs: device arrays of `planes` entries.  Three launches, no memset. */
+int rsuper_deflate_planes(const uint8_t* src, long plane_stride, size_t n, int planes, int pitch, const uint32_t* table, const uint32_t* header,
+                          int header_bits, uint8_t* out, unsigned long long* offsets, unsigned long long* sizes, uint32_t* crcs, void* workspace,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 #include "loss.hpp"
 #include "morph.hpp"
 #include "optim.hpp"
+#include "deflate.hpp"
 #include "../../include/rsuper_hip.h"
 
 #define ST(s) ((hipStream_t)(s))
@@ -893,6 +894,19 @@ int rsuper_adamw_ema_step_dyn(int n, void* const* host_p, void* const* host_g, v
     a.lr = 0.f; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
     a.step_size = 0.f; a.sqrt_bc2 = 1.f; a.ema_alpha = 0.f; a.max_norm = max_norm; a.dyn = dyn;
     return for_chunks(n, host_p, host_g, host_m, host_v, host_ema, host_numel, [&](const MTChunk& c) { return rs_launch_adamw_ema(c, a, total_sq, ST(stream)); });
+}
+
+size_t rsuper_deflate_bound(size_t n) { return rs_deflate_bound(n); }
+size_t rsuper_deflate_workspace_bytes(int planes, size_t n) { return planes < 1 ? 0 : rs_deflate_workspace_bytes(planes, n); }
+int rsuper_deflate_chunk_bytes(void) { return DF_CHUNK; }
+int rsuper_deflate_segment_bytes(void) { return DF_SEG; }
+int rsuper_deflate_planes(const uint8_t* src, long plane_stride, size_t n, int planes, int pitch, const uint32_t* table, const uint32_t* header,
+                          int header_bits, uint8_t* out, unsigned long long* offsets, unsigned long long* sizes, uint32_t* crcs, void* workspace,
+                          void* stream) {
+    if (pitch < 0 || pitch > DF_MAX_PITCH || planes < 1 || planes > 65535 || n >= ((size_t)1 << 32)) return RS_ERR_ARG;
+    if (!table || !header || header_bits < 3 || header_bits > DF_MAX_HEADER_BITS || !out || !offsets || !sizes || !crcs) return RS_ERR_ARG;
+    if (n > 0 && (!src || !workspace || plane_stride < (long)n)) return RS_ERR_ARG;
+    return rs_launch_deflate_planes(src, plane_stride, (long)n, planes, pitch, table, header, header_bits, out, offsets, sizes, crcs, workspace, ST(stream));
 }
 
 }  // extern "C"

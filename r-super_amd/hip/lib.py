@@ -184,6 +184,11 @@ _SIGS = {
     'rsuper_bits_open_workspace_bytes': (c_long, [c_int] * 3),
     'rsuper_bits_open': (c_int, [P] + [c_int] * 7 + [P, c_long, P, P, P, P, P]),
     'rsuper_label_remap': (c_int, [P, c_int, c_int, c_int, c_long, c_int, P, c_int, c_int, P, P, P]),
+    'rsuper_deflate_bound': (c_size_t, [c_size_t]),
+    'rsuper_deflate_workspace_bytes': (c_size_t, [c_int, c_size_t]),
+    'rsuper_deflate_chunk_bytes': (c_int, []),
+    'rsuper_deflate_segment_bytes': (c_int, []),
+    'rsuper_deflate_planes': (c_int, [P, c_long, c_size_t, c_int, c_int, P, P, c_int, P, P, P, P, P, P]),
     'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

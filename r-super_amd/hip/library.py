@@ -51,6 +51,8 @@ whole-case preprocessing and resampling (inference/preprocess.py, inference/resa
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
 report-guided pseudo-label refinement (baselines/pseudo_labels/pseudo_label_report_refinement.py; no derivative):
     torch.ops.rsuper.lesion_candidates(prob, n_lesions, peak_cut, min_voxels, min_peak, batch) -> (uint8 masks, per-plane state words)
+compressed mask files (inference/npz_writer.py; no derivative):
+    torch.ops.rsuper.deflate_planes(src, n, plane_stride, planes, pitch, table, header, header_bits) -> (streams back to back, offsets / sizes / CRCs)
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -291,3 +293,10 @@ def install_pseudo_label_ops(lesion_candidates):
     return _install_plain('pseudo_label', (
         ('lesion_candidates', '(Tensor prob, int[] n_lesions, float peak_cut, int min_voxels, float min_peak, int batch) -> (Tensor mask, Tensor state)',
          lesion_candidates),))[0]
+
+
+def install_deflate_ops(deflate_planes):
+    """The DEFLATE encoder of inference/npz_writer.py (on its first use): compressed bytes have no derivative."""
+    return _install_plain('deflate', (
+        ('deflate_planes', '(Tensor src, int n, int plane_stride, int planes, int pitch, Tensor table, Tensor header, int header_bits) -> (Tensor, Tensor)',
+         deflate_planes),))[0]

@@ -8,3 +8,4 @@ from .detection import detection, detection_binary, zoom_shape  # noqa: F401
 from .preprocess import normalize_ct, pad_to_training_size, unpad_img, preprocess_array  # noqa: F401
 from .resample import resample_image_with_gpu, predict_case  # noqa: F401
 from .scoring import score_case  # noqa: F401
+from .npz_writer import deflate_device, savez_compressed_device, save_planes_npz, gzip_device  # noqa: F401

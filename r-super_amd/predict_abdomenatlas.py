@@ -11,6 +11,10 @@ section 3b has the hand-wired path).  Outputs under `<save_path>/<dataset>/<fold
     predictions_raw/<class>.npz      float32 probabilities (--save_probabilities: all classes, --save_probabilities_lesions: lesion classes)
     *.nii.gz copies                  only when nibabel imports
 
+--device_compress deflates the uint8 masks (per class or --packed) on the device and reads back the compressed bytes only (inference/npz_writer.py):
+the same files, keys and arrays under np.load, other compressed bytes.  Without it every byte written is np.savez_compressed's.  The float32
+probabilities stay on the host path.
+
 --score measures every case while it is still on the device (inference.score_case) and appends the rows to tumor_detection_results.csv and, with
 probabilities, tumor_detection_results_th0.1.csv ... in the save path; with --not_save_binary nothing has to be written and read back.
 
@@ -59,6 +63,7 @@ def get_parser(argv=None, config_root=None):
     p.add_argument('--current_part', type=int, default=0)
     p.add_argument('--gpu', type=str, default='0')
     p.add_argument('--packed', action='store_true', help='one bit-packed predictions.npz per case instead of one file per class')
+    p.add_argument('--device_compress', action='store_true', help='deflate the saved masks on the device; the files load to the same arrays')
     p.add_argument('--score', action='store_true', help='measure each case on the device and append the detection CSV rows')
     p.add_argument('--spacing_csv', type=str, default=None, help='CSV with BDMAP_ID and one spacing column per array axis (default: 1 mm)')
     p.add_argument('--th', type=float, default=0.5, help='threshold that binarises a mask for --score')
@@ -211,13 +216,30 @@ def _save_nifti_copy(arr, path):
     nib.save(nib.Nifti1Image(arr, np.eye(4)), path)
 
 
-def write_binary(case_dir, pred_dict, names, packed):
-    """One device-to-host read of the saved planes; --packed packs them on the device first (8x fewer bytes over the bus and on disk)."""
+def write_binary(case_dir, pred_dict, names, packed, device_compress=False):
+    """One device-to-host read of the saved planes; --packed packs them on the device first (8x fewer bytes over the bus and on disk);
+    --device_compress deflates them on the device too, and the read is of the compressed bytes."""
     stack = torch.stack([pred_dict[n].to(torch.uint8) for n in names])
     if packed:
         from .training.dataset.packed import pack_bits_device
-        bits = pack_bits_device(stack).packed[0].cpu().numpy()
-        np.savez_compressed(os.path.join(case_dir, 'predictions.npz'), arr_0=bits, classes=np.array(names))
+        bits = pack_bits_device(stack).packed[0]
+        if device_compress:
+            from .inference.npz_writer import savez_compressed_device
+            savez_compressed_device(os.path.join(case_dir, 'predictions.npz'), table='mask', arr_0=bits, classes=np.array(names))
+            return
+        np.savez_compressed(os.path.join(case_dir, 'predictions.npz'), arr_0=bits.cpu().numpy(), classes=np.array(names))
+        return
+    if device_compress:
+        from .inference.npz_writer import save_planes_npz
+        os.makedirs(os.path.join(case_dir, 'predictions'), exist_ok=True)
+        save_planes_npz([os.path.join(case_dir, 'predictions', n + '.npz') for n in names], stack, table='mask')
+        try:
+            import nibabel  # noqa: F401
+        except ImportError:
+            return
+        host = stack.cpu().numpy()
+        for k, n in enumerate(names):
+            _save_nifti_copy(host[k], os.path.join(case_dir, 'predictions', n + '.nii.gz'))
         return
     host = stack.cpu().numpy()
     os.makedirs(os.path.join(case_dir, 'predictions'), exist_ok=True)
@@ -303,7 +325,7 @@ def main(argv=None, config_root=None):
             if not args.not_save_binary or want_raw:
                 os.makedirs(case_dir, exist_ok=True)
             if not args.not_save_binary:
-                write_binary(case_dir, pred_dict, names, args.packed)
+                write_binary(case_dir, pred_dict, names, args.packed, args.device_compress)
             if raw_dict is not None:
                 write_raw(case_dir, raw_dict, names if args.save_probabilities else [n for n in names if any(w in n for w in LESION_WORDS)])
             clock('write', t)

@@ -1,5 +1,5 @@
 """python -m rsuper_amd.tools.refine_pseudo_labels --input_dir DIR --metadata CSV --out_npz_dir DIR [--parts N --part i]
-                                                  [--label_list YAML --organs_path DIR --tgt_path DIR [--packed]]
+                                                  [--label_list YAML --organs_path DIR --tgt_path DIR [--packed]] [--device_compress]
 
 The report-refined pseudo-label baseline (the reference's baselines/pseudo_labels/pseudo_label_report_refinement.py main, npz branch) with the
 candidate extraction on the device.  --input_dir holds one folder per case, `<ID>.npz/` (or, when there is none, `<ID>.nii.gz/`), with the raw
@@ -15,6 +15,9 @@ With --tgt_path (and --label_list, --organs_path) every case refined in this run
 (plane order: the sorted `<organs_path>/list/label_names.yaml`) into the training label `<tgt_path>/<ID>_gt.npz` (merge_pseudo_labels; the labels of
 --label_list in sorted order), or with --packed into the bit-packed `<ID>_gt.npy` tools.pack_dataset writes; `<ID>.npz` and `list/label_names.yaml`
 are written next to it.
+
+--device_compress deflates the mask files and `<ID>_gt.npz` on the device (inference/npz_writer.py): the same keys (`mask`, `arr_0`) and arrays under
+np.load, other compressed bytes.  Without it every byte written is np.savez_compressed's.
 
 Deviations from the reference, on purpose: the id of a `<ID>.nii.gz/` folder is `<ID>` (Path.stem leaves `<ID>.nii`, which matches no metadata row);
 the `list/` folder of the output tree is not listed as a case; there is no NIfTI output tree.  .nii.gz probabilities need nibabel, which this package
@@ -115,7 +118,7 @@ def copy_predictions(folder, out_root):
         dst.mkdir(parents=True, exist_ok=True)
 
 
-def process_case(folder, meta, out_root, device='cuda'):
+def process_case(folder, meta, out_root, device='cuda', device_compress=False):
     """One folder -> (id, included, {class: device mask})."""
     import torch
     from ..baselines.pseudo_labels import refine_case
@@ -129,8 +132,14 @@ def process_case(folder, meta, out_root, device='cuda'):
     if included:
         dst = Path(out_root) / cid
         dst.mkdir(parents=True, exist_ok=True)
-        for name, m in masks.items():
-            np.savez_compressed(str(dst / (name + '.npz')), mask=m.cpu().numpy().astype(np.uint8))
+        if device_compress and masks:
+            from ..inference.npz_writer import save_planes_npz
+            names = list(masks)
+            save_planes_npz([str(dst / (name + '.npz')) for name in names], torch.stack([masks[name].to(torch.uint8) for name in names]), key='mask',
+                            table='mask')
+        else:
+            for name, m in masks.items():
+                np.savez_compressed(str(dst / (name + '.npz')), mask=m.cpu().numpy().astype(np.uint8))
     return cid, included, masks
 
 
@@ -144,6 +153,9 @@ def write_training_label(cid, masks, a, labels, organ_names, device='cuda'):
     stack = merge_pseudo_labels(torch.from_numpy(np.ascontiguousarray(organs)).to(device), organ_names, masks, labels, packed=a.packed)
     if a.packed:
         np.save(os.path.join(a.tgt_path, cid + '_gt.npy'), stack.packed[0].cpu().numpy())
+    elif a.device_compress and stack.dtype in (torch.uint8, torch.int8, torch.bool):
+        from ..inference.npz_writer import savez_compressed_device
+        savez_compressed_device(os.path.join(a.tgt_path, cid + '_gt.npz'), stack, table='mask')
     else:
         np.savez_compressed(os.path.join(a.tgt_path, cid + '_gt.npz'), stack.cpu().numpy())
     shutil.copy(ct, os.path.join(a.tgt_path, cid + '.npz'))
@@ -160,6 +172,7 @@ def main(argv=None):
     p.add_argument('--organs_path', type=Path, default=None, help='<ID>.npz, <ID>_gt.npz and list/label_names.yaml of the organ labels (with --tgt_path)')
     p.add_argument('--tgt_path', type=Path, default=None, help='also write the merged training labels here')
     p.add_argument('--packed', action='store_true', help='write the merged label bit-packed, as tools.pack_dataset does')
+    p.add_argument('--device_compress', action='store_true', help='deflate the mask files and <ID>_gt.npz on the device (same arrays under np.load)')
     a = p.parse_args(argv)
     if not 0 <= a.part < a.parts:
         raise ValueError(f'--part {a.part} is outside 0 .. {a.parts - 1}')
@@ -197,7 +210,7 @@ def main(argv=None):
                 raise ValueError(f'{a.label_list} or {a.organs_path}/list/label_names.yaml is missing or empty')
             dump_yaml(a.tgt_path / 'list' / 'label_names.yaml', labels)
         for d in mine:
-            cid, ok, masks = process_case(d, meta, out)
+            cid, ok, masks = process_case(d, meta, out, device_compress=True) if a.device_compress else process_case(d, meta, out)
             (kept if ok else skipped).add(cid)
             if ok and a.tgt_path is not None:
                 write_training_label(cid, masks, a, labels, organ_names)

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Times `python -m rsuper_amd.predict_abdomenatlas` on synthetic cases, stage by stage (read, predict, post-process, measure, write), for a tiny
 UNet (base 8, 7 classes, 32^3 window, 64^3 cases) and the config-2 UNet (base 32, 26 PanTS classes, 96^3 window, 192^3 cases, bf16), in three
-output modes: `--score --not_save_binary` (nothing written but the CSV rows), one .npz per class, and `--packed`.  Each mode runs twice with
+output modes: `--score --not_save_binary` (nothing written but the CSV rows), one .npz per class, and `--packed`; with --device-compress the two
+saving modes are taken again with the command's `--device_compress` (the DEFLATE pass on the device, inference/npz_writer.py).  Each mode runs twice with
 --overwrite; the second run is reported (the first pays the module loads).  For comparison the reference's measurement as it stands
 (test_with_reports.detection's steps in scipy, on host copies of the same lesion planes) is timed on the same box where scipy imports.
 Writes profiles/predict_bench.json and prints it as one JSON line.
 
-    python tools/bench_predict.py [--cases 3] [--no-config2] [--no-cpu]"""
+    python tools/bench_predict.py [--cases 3] [--no-config2] [--no-cpu] [--device-compress]"""
 import argparse
 import json
 import os
@@ -100,6 +101,7 @@ def main():
     ap.add_argument('--cases', type=int, default=3)
     ap.add_argument('--no-config2', action='store_true')
     ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--device-compress', action='store_true', help='also time the two saving modes with --device_compress')
     a = ap.parse_args()
     import synth
     from rsuper_amd.hip import lib
@@ -117,6 +119,9 @@ def main():
                    'per_class_files': run_mode(root, 'f', []),
                    'packed': run_mode(root, 'p', ['--packed']),
                    'score_and_per_class_files': run_mode(root, 'sf', ['--score'])}
+            if a.device_compress:
+                res['per_class_files_device_compress'] = run_mode(root, 'fd', ['--device_compress'])
+                res['packed_device_compress'] = run_mode(root, 'pd', ['--packed', '--device_compress'])
             if not a.no_cpu:
                 res['reference_measurement_on_host'] = cpu_measure(root, classes, win, a.cases)
             out[name] = res
