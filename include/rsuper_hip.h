@@ -902,6 +902,40 @@ int rsuper_deflate_planes(const uint8_t* src, long plane_stride, size_t n, int p
                           int header_bits, uint8_t* out, unsigned long long* offsets, unsigned long long* sizes, uint32_t* crcs, void* workspace,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * NIfTI front and back end of a case -- reorientation, the cubic B-spline prefilter and the "B-spline in-plane, nearest along z" resample that
+ * precede the clip in predict_abdomenatlas.py preprocess (:333-343, dataset_conversion/utils.py:10-47), and masks back in the file's voxel order.
+ * csrc/nifti.hip; the tables and headers are made on the host (inference/nifti.py).
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_NII_U8 0
+#define RSUPER_NII_I8 1
+#define RSUPER_NII_I16 2
+#define RSUPER_NII_U16 3
+#define RSUPER_NII_I32 4
+#define RSUPER_NII_F32 5
+/* src: device, the file's voxel buffer of n_src elements of `dtype`.  Canonical voxel (z, y, x) is element offset + z * sz + y * sy + x * sx of it
+ * (a flipped axis has a negative stride) and is scaled as (float)v * slope + inter in f32 unless slope == 1 and inter == 0.
+ * out: device [Z][Y][X] f32.  prefilter == 0: the scaled samples.  Otherwise the cubic B-spline coefficients of every slice: the causal and
+ * anticausal recursion with pole sqrt(3) - 2 along x, then along y (in place), whole-sample mirror boundaries, the start sums cut where |z1|^k
+ * falls below 2^-30 (16 terms); a line of one sample is the sample.  One launch, two with prefilter (and Y > 1).
+ * A side above 4096 -> RSUPER_ERR_UNSUPPORTED.  Null or misaligned pointers, out == src, an unknown dtype, non-positive sizes or strides that
+ * leave the buffer -> RSUPER_ERR_ARG, checked before anything is launched. */
+int rsuper_nifti_load_prefilter(const void* src, int dtype, long n_src, int Z, int Y, int X, long sz, long sy, long sx, long offset, float slope,
+                                float inter, int prefilter, float* out, void* stream);
+/* coef: device [Z][Y][X] f32 coefficients.  ix, wx [Xo][4] and iy, wy [Yo][4] (device int32 / f32): the four source indices (mirror applied) and
+ * weights of an output index, ix[o][0] < 0 = outside; iz [Zo] int32: the source slice, < 0 = outside.
+ * out [Zo][Yo][Xo] f32 = sum_j wy[j] sum_i wx[i] coef[iz][iy[j]][ix[i]], or outside_value where any axis is outside.  Indices are clamped into the
+ * volume before they are used.  One launch.  Input sides above 4096 or Zo above 65535 -> RSUPER_ERR_UNSUPPORTED; null or misaligned pointers,
+ * out == coef, non-positive sizes -> RSUPER_ERR_ARG. */
+int rsuper_bspline_resample(const float* coef, int Z, int Y, int X, const int* ix, const float* wx, const int* iy, const float* wy, const int* iz,
+                            float* out, int Zo, int Yo, int Xo, float outside_value, void* stream);
+/* src: device [C][Z][Y][X] uint8 (canonical).  Plane c is written in the file's voxel order (i fastest, ni * nj * nk == Z * Y * X < 2^31) at
+ * dst + dst_offset + c * plane_stride: file voxel (i, j, k) = src plane element coff + i * ci + j * cj + k * ck.  dst holds dst_bytes bytes; the
+ * bytes in front of and between the planes (file headers) are left as they are.  One launch.  A plane that leaves dst, strides that leave the
+ * source plane, overlapping buffers, C outside 1..65535 -> RSUPER_ERR_ARG. */
+int rsuper_reorient_store(const uint8_t* src, int C, int Z, int Y, int X, uint8_t* dst, long dst_bytes, long dst_offset, long plane_stride, int ni,
+                          int nj, int nk, long ci, long cj, long ck, long coff, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,7 +189,10 @@ _SIGS = {
     'rsuper_deflate_chunk_bytes': (c_int, []),
     'rsuper_deflate_segment_bytes': (c_int, []),
     'rsuper_deflate_planes': (c_int, [P, c_long, c_size_t, c_int, c_int, P, P, c_int, P, P, P, P, P, P]),
-    'rsuper_grad_sqnorm': (c_int, [c_int, P, P, P, P]),
+    'rsuper_nifti_load_prefilter': (c_int, [P, c_int, c_long, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_float, c_float, c_int, P, P]),
+    'rsuper_bspline_resample': (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
+    'rsuper_reorient_store': (c_int, [P, c_int, c_int, c_int, c_int, P, c_long, c_long, c_long, c_int, c_int, c_int, c_long, c_long, c_long, c_long, P]),
+    'rsuper_grad_sqnorm':(c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),
     'rsuper_adamw_ema_step_dyn': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P, P, P]),

@@ -53,6 +53,10 @@ report-guided pseudo-label refinement (baselines/pseudo_labels/pseudo_label_repo
     torch.ops.rsuper.lesion_candidates(prob, n_lesions, peak_cut, min_voxels, min_peak, batch) -> (uint8 masks, per-plane state words)
 compressed mask files (inference/npz_writer.py; no derivative):
     torch.ops.rsuper.deflate_planes(src, n, plane_stride, planes, pitch, table, header, header_bits) -> (streams back to back, offsets / sizes / CRCs)
+NIfTI front and back end of a case (inference/nifti_device.py; no derivative):
+    torch.ops.rsuper.nifti_load_prefilter(raw, dtype, size, strides, offset, slope, inter, prefilter) -> canonical (Z, Y, X) float32 samples / coefficients
+    torch.ops.rsuper.bspline_resample(coef, ix, wx, iy, wy, iz, outside_value) -> (Zo, Yo, Xo) float32
+    torch.ops.rsuper.reorient_store(stack, dst, dst_offset, plane_stride, shape_ijk, strides, offset)       (writes the planes into dst)
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -300,3 +304,14 @@ def install_deflate_ops(deflate_planes):
     return _install_plain('deflate', (
         ('deflate_planes', '(Tensor src, int n, int plane_stride, int planes, int pitch, Tensor table, Tensor header, int header_bits) -> (Tensor, Tensor)',
          deflate_planes),))[0]
+
+
+def install_nifti_ops(load_prefilter, bspline_resample, reorient_store):
+    """The NIfTI operators of inference/nifti_device.py (at the end of that module's setup): a resampled network input and stored masks have no
+    derivative."""
+    return _install_plain('nifti', (
+        ('nifti_load_prefilter', '(Tensor raw, int dtype, int[] size, int[] strides, int offset, float slope, float inter, bool prefilter) -> Tensor',
+         load_prefilter),
+        ('bspline_resample', '(Tensor coef, Tensor ix, Tensor wx, Tensor iy, Tensor wy, Tensor iz, float outside_value) -> Tensor', bspline_resample),
+        ('reorient_store', '(Tensor stack, Tensor(a!) dst, int dst_offset, int plane_stride, int[] shape_ijk, int[] strides, int offset) -> ()',
+         reorient_store)))

@@ -492,7 +492,19 @@ def save_planes_npz(paths, stack, key='arr_0', table='fixed', timings=None):
         timings['file'] = timings.get('file', 0.0) + time.perf_counter() - t0
 
 
+def gzip_member(stream, crc, size):
+    """The bytes of a .gz file around a raw DEFLATE stream of `size` bytes with CRC-32 `crc`: 10-byte header, the stream, CRC-32 and size."""
+    return b'\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff' + stream + struct.pack('<II', crc, size & 0xFFFFFFFF)
+
+
 def gzip_device(tensor, table='fixed'):
     """The bytes of a .gz file of the tensor's bytes (gzip.decompress gives them back): 10-byte header, the device stream, CRC-32 and size."""
     (stream,), (crc,) = deflate_device(tensor.reshape((1,) + tuple(tensor.shape)), pitch=_row_pitch(tensor), table=table)
-    return b'\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff' + stream + struct.pack('<II', crc, tensor.numel() & 0xFFFFFFFF)
+    return gzip_member(stream, crc, tensor.numel())
+
+
+def gzip_planes_device(storage, n, plane_stride, planes, pitch=0, table='fixed'):
+    """gzip_device for `planes` byte planes of n bytes lying plane_stride apart in flat one-byte device storage: one .gz file's bytes per plane from one
+    device call (deflate_strided)."""
+    streams, crcs = deflate_strided(storage, n, plane_stride, planes, pitch, table)
+    return [gzip_member(s, c, n) for s, c in zip(streams, crcs)]

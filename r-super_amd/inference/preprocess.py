@@ -6,8 +6,9 @@ Here the z-score is two launches (csrc/resample.hip): `rsuper_ct_stats` writes p
 them in every block and writes (clip(x) - mean) / std straight into the zero-padded volume.  The input may stay int16, as a CT is stored.
 `torch.ops.rsuper.ct_normalize` is the dispatcher entry (CUDA key only; a CPU tensor raises RSuperHipError).
 
-Out of scope: NIfTI I/O, reorientation and the SimpleITK B-spline resample to the target spacing that precede the clip in `preprocess` stay with
-the caller; so do the nii-path `postprocess` organ gate (sitk.BinaryDilate with ITK's ball element) and multi-GPU case sharding.
+NIfTI I/O, reorientation and the B-spline resample to the target spacing that precede the clip in `preprocess` are inference/nifti.py and
+inference/nifti_device.py (load_nifti_device).  Out of scope: the nii-path `postprocess` organ gate (sitk.BinaryDilate with ITK's ball element)
+and multi-GPU case sharding.
 """
 import torch
 

@@ -8,8 +8,8 @@ values, uint8 labels or `value > threshold`.  `torch.ops.rsuper.resample3d` is t
 RSuperHipError).  The coordinate arithmetic is F.interpolate's on the reference's path: legacy 'nearest', and 'trilinear' with
 align_corners=True, in float32.
 
-Out of scope: NIfTI I/O and reorientation, the nii-path `postprocess` organ gate (sitk.BinaryDilate with ITK's radius-3 ball element) and
-multi-GPU case sharding.
+NIfTI I/O and reorientation around predict_case are inference/nifti_device.py (predict_nifti_case, save_nifti_masks).  Out of scope: the
+nii-path `postprocess` organ gate (sitk.BinaryDilate with ITK's radius-3 ball element) and multi-GPU case sharding.
 """
 import numpy as np
 import torch

@@ -2,10 +2,15 @@
 then per case predict_case -> postprocess_npz -> write, with the reference's flag names.  The next case is read by one background thread while the
 device works on the current one.
 
-Inputs are `<id>.npz` (arr_0) or the `<id>.npy` files tools/pack_dataset.py writes; a NIfTI input is refused (no SimpleITK here, INTEGRATION
-section 3b has the hand-wired path).  Outputs under `<save_path>/<dataset>/<folder of the first checkpoint>/<case>/`:
+Inputs are `<id>.npz` (arr_0) or the `<id>.npy` files tools/pack_dataset.py writes.  A NIfTI input is refused unless --nifti is given; with it
+`<id>.nii.gz` and `<id>/ct.nii.gz` are read by inference/nifti.py in the reader thread (no SimpleITK, no nibabel), reoriented and resampled to 1 mm
+on the device (inference.predict_nifti_case), predicted, and saved as predictions/<class>.nii.gz on the scan's own grid, in
+its own voxel order, with its affine (inference.save_nifti_masks); --score takes the spacing from the header unless --spacing_csv names the case;
+the probabilities keep going out as .npz; --packed and --device_compress do not apply to such a case.
+Outputs under `<save_path>/<dataset>/<folder of the first checkpoint>/<case>/`:
 
     predictions/<class>.npz          uint8 masks (default)
+    predictions/<class>.nii.gz       uint8 masks of a NIfTI case (--nifti), compressed on the device
     predictions.npz                  --packed: arr_0 = np.packbits(masks, axis=0) of the saved classes (packed on the device; the training-label
                                      layout) and `classes`, their names
     predictions_raw/<class>.npz      float32 probabilities (--save_probabilities: all classes, --save_probabilities_lesions: lesion classes)
@@ -66,6 +71,8 @@ def get_parser(argv=None, config_root=None):
     p.add_argument('--device_compress', action='store_true', help='deflate the saved masks on the device; the files load to the same arrays')
     p.add_argument('--score', action='store_true', help='measure each case on the device and append the detection CSV rows')
     p.add_argument('--spacing_csv', type=str, default=None, help='CSV with BDMAP_ID and one spacing column per array axis (default: 1 mm)')
+    p.add_argument('--nifti', action='store_true', help='accept <id>.nii.gz and <id>/ct.nii.gz cases: read, reorient and resample them on the device and '
+                   'save the masks as .nii.gz on the scan\'s own grid (ignored for .npz / .npy cases)')
     p.add_argument('--th', type=float, default=0.5, help='threshold that binarises a mask for --score')
     args = p.parse_args(argv)
     path = args.config
@@ -110,9 +117,13 @@ def list_ids(args):
                 break
         else:
             raise ValueError('Path not found')
-    for i in ids:
-        refuse_nifti(i)
-    kept = sorted(i for i in ids if os.path.exists(os.path.join(args.img_path, i)) and i.endswith(('.npz', '.npy')))
+    nifti = getattr(args, 'nifti', False)
+    if nifti:           # a case folder that holds ct.nii.gz is the case <folder>/ct.nii.gz
+        ids = [i + '/ct.nii.gz' if os.path.isfile(os.path.join(args.img_path, i, 'ct.nii.gz')) else i for i in ids]
+    else:
+        for i in ids:
+            refuse_nifti(i)
+    kept = sorted(i for i in ids if os.path.exists(os.path.join(args.img_path, i)) and i.endswith(('.npz', '.npy') + (('.nii.gz',) if nifti else ())))
     print(f'After removing missing cases, {len(kept)} ids remain. Number of removed files: {len(ids) - len(kept)}')
     return kept
 
@@ -121,11 +132,12 @@ def saved_classes(class_list, args):
     return [c for c in class_list if 'pancrea' in c] if args.save_pancreas_lesion_only else list(class_list)
 
 
-def already_predicted(case_dir, class_list):
-    """Every class of class_list is saved: predictions/<class>.npz for all of them, or a packed predictions.npz that names them all."""
+def already_predicted(case_dir, class_list, ext='.npz'):
+    """Every class of class_list is saved: predictions/<class>.npz (.nii.gz for a NIfTI case) for all of them, or a packed predictions.npz that names
+    them all."""
     pred_dir = os.path.join(case_dir, 'predictions')
     if os.path.isdir(pred_dir):
-        stems = {f[:-4] for f in os.listdir(pred_dir) if f.endswith('.npz')}
+        stems = {f[:-len(ext)] for f in os.listdir(pred_dir) if f.endswith(ext)}
         if set(class_list).issubset(stems):
             return True
     packed = os.path.join(case_dir, 'predictions.npz')
@@ -140,7 +152,8 @@ def filter_already_predicted(ids, save_path, class_list, overwrite, scored_ids=(
     whose row is already in the CSV)."""
     if overwrite:
         return ids
-    kept = [i for i in ids if not (already_predicted(os.path.join(save_path, case_id_of(i)), class_list) or case_id_of(i) in scored_ids)]
+    kept = [i for i in ids if not (already_predicted(os.path.join(save_path, case_id_of(i)), class_list, '.nii.gz' if i.endswith('.nii.gz') else '.npz')
+                                   or case_id_of(i) in scored_ids)]
     print(f'Ids after filtering: {len(kept)} / {len(ids)}')
     return kept
 
@@ -179,7 +192,13 @@ def _load_array(path):
 
 
 def load_case(args, img_name, class_list):
-    """(HU array, pancreas mask or None) of a case; the label of --predict_pancreas_only is <id>_gt.npz / .npy, bit-packed or one byte per class."""
+    """(HU array, pancreas mask or None) of a case; the label of --predict_pancreas_only is <id>_gt.npz / .npy, bit-packed or one byte per class.
+    With --nifti a NIfTI case comes back as the inference.nifti.NiftiVolume of the file (read and inflated here, in the reader thread)."""
+    if getattr(args, 'nifti', False) and 'nii.gz' in img_name:
+        if args.predict_pancreas_only:
+            raise ValueError('You cannot predict only pancreas with nii.gz files, please use npz files.')
+        from .inference.nifti import read_nifti
+        return read_nifti(os.path.join(args.img_path, img_name)), None
     refuse_nifti(img_name)
     path = os.path.join(args.img_path, img_name)
     hu = _load_array(path)
@@ -262,7 +281,8 @@ def main(argv=None, config_root=None):
     """Returns the list of predicted case ids and the seconds per stage {'read', 'predict', 'postprocess', 'measure', 'write'}."""
     import yaml
     from .hip import lib
-    from .inference import postprocess_npz
+    from .inference import postprocess_npz, predict_nifti_case, save_nifti_masks
+    from .inference.nifti import NiftiVolume
     from .inference.scoring import score_case
     from .train_ddp import load_old_classes
     args = get_parser(argv, config_root)
@@ -310,7 +330,11 @@ def main(argv=None, config_root=None):
             if k + 1 < len(ids):
                 nxt = reader.submit(load_case, args, ids[k + 1], class_list)
             t = clock('read', t)
-            pred_dict, raw = predict_one(models, hu, pancreas, args, class_list)
+            geom = None
+            if isinstance(hu, NiftiVolume):
+                pred_dict, raw, geom = predict_nifti_case(models, hu, args, class_list, return_raw=True)
+            else:
+                pred_dict, raw = predict_one(models, hu, pancreas, args, class_list)
             t = clock('predict', t)
             raw_dict = postprocess_npz(raw, class_list, args) if want_raw else None
             pred_dict = {n: pred_dict[n] for n in names}
@@ -319,12 +343,15 @@ def main(argv=None, config_root=None):
             t = clock('postprocess', t)
             case_dir = os.path.join(args.save_path, case_id)
             if args.score:
-                row, rows = score_case(pred_dict, raw_dict, names, spacings.get(case_id, (1.0, 1.0, 1.0)), th=args.th, case_id=case_id)
+                row, rows = score_case(pred_dict, raw_dict, names, spacings.get(case_id, (1.0, 1.0, 1.0) if geom is None else geom.spacing[::-1]),
+                                       th=args.th, case_id=case_id)
                 append_rows(args.save_path, row, rows)
                 t = clock('measure', t)
             if not args.not_save_binary or want_raw:
                 os.makedirs(case_dir, exist_ok=True)
-            if not args.not_save_binary:
+            if not args.not_save_binary and geom is not None:
+                save_nifti_masks(case_dir, pred_dict, names, geom)
+            elif not args.not_save_binary:
                 write_binary(case_dir, pred_dict, names, args.packed, args.device_compress)
             if raw_dict is not None:
                 write_raw(case_dir, raw_dict, names if args.save_probabilities else [n for n in names if any(w in n for w in LESION_WORDS)])
