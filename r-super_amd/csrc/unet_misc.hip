@@ -75,10 +75,19 @@ __device__ __forceinline__ void block_channel_sums(const float* s1, const float*
         }
     }
     __syncthreads();
+    // f32 storage (KP == 4, the parity mode): the VL lane sums are added in f64 and rounded to f32 once.  A sequential f32 sum over up to 256 lanes costs
+    // up to VL roundings of the row, which var = E[y^2] - mean^2 amplifies by E[y^2] / var: rstd of a pooled 8^3 tensor was off by 1.4e-6 against
+    // float64, over the 1e-6 that mode's pool check allows (4.5e-7 at worst now).  bf16 storage keeps its f32 sum, and with it every bit of its rows.
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float a = 0.f, b = 0.f;
-        for (int v = 0; v < VL; ++v) { a += red[(v * C + c) * 2]; b += red[(v * C + c) * 2 + 1]; }
-        part_blk[c * 2] = a; part_blk[c * 2 + 1] = b;
+        if constexpr (KP == 4) {
+            double a = 0.0, b = 0.0;
+            for (int v = 0; v < VL; ++v) { a += (double)red[(v * C + c) * 2]; b += (double)red[(v * C + c) * 2 + 1]; }
+            part_blk[c * 2] = (float)a; part_blk[c * 2 + 1] = (float)b;
+        } else {
+            float a = 0.f, b = 0.f;
+            for (int v = 0; v < VL; ++v) { a += red[(v * C + c) * 2]; b += red[(v * C + c) * 2 + 1]; }
+            part_blk[c * 2] = a; part_blk[c * 2 + 1] = b;
+        }
     }
 }
 

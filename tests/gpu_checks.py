@@ -506,7 +506,7 @@ def check_pool(mode):
     y.backward(to_cl(go, dt))
     torch.cuda.synchronize()
     e = max(relerr(from_cl(y.detach()), y_ref.detach()), relerr(from_cl(xc.grad), x.grad),
-            relerr(mr.cpu()[..., 0], stats_ref(y_ref.detach())[..., 0]))
+            relerr(mr.cpu()[..., 0], stats_ref(y_ref.detach())[..., 0]), relerr(mr.cpu()[..., 1], stats_ref(y_ref.detach())[..., 1]))
     if mode == 'f32':
         e = max(e, relerr(from_cl(y.detach()), T(g['pool_y'])), relerr(from_cl(xc.grad), T(g['pool_dx'])))
     return result(f'maxpool[{mode}]', e, 1e-6 if mode == 'f32' else 1e-2)

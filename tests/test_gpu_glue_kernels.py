@@ -5,7 +5,7 @@ statistics rows `part`, per-block loss sums -- must be equal bit for bit; output
 
 Shapes: the UNet step's own (config 2: B = 2, 96^3, base 32: every level of the tail and of pooling, the four up-sampling outputs 96^3 x 64, 48^3 x 128,
 24^3 x 256, 12^3 x 320), one ragged case per kernel (odd sizes, C = 8), and the f32 mode.  The trilinear backward and plane_partials_bwd kernels are
-unchanged and are not compared here."""
+unchanged and are not compared here.  The independent anchor of this bit-for-bit chain is tests/test_gpu_glue_ref.py: the default kernels against float64."""
 import numpy as np
 import pytest
 import torch
