@@ -782,6 +782,10 @@ long rsuper_ct_stats_workspace_bytes(void);
 int rsuper_ct_stats(const void* x, int dtype, int D, int H, int W, float lo, float hi, void* workspace, long workspace_bytes, void* stream);
 int rsuper_ct_normalize(const void* x, int dtype, int D, int H, int W, float lo, float hi, const void* workspace, long workspace_bytes, float* out,
                         int Do, int Ho, int Wo, int z_lo, int y_lo, int x_lo, float* mean_std, void* stream);
+/* rsuper_ct_normalize with the population standard deviation: sqrt((Q - N mean^2) / N), numpy's np.std (ddof = 0), which dataset_conversion/nii2npz.py
+ * :71-74 uses.  The same kernel, arguments and checks; N == 1 gives 0 / 0 = NaN. */
+int rsuper_ct_normalize_pop(const void* x, int dtype, int D, int H, int W, float lo, float hi, const void* workspace, long workspace_bytes, float* out,
+                            int Do, int Ho, int Wo, int z_lo, int y_lo, int x_lo, float* mean_std, void* stream);
 int rsuper_pad_box(const void* x, int dtype, int D, int H, int W, float* out, int Do, int Ho, int Wo, int z_lo, int y_lo, int x_lo, void* stream);
 /* One launch: src [C][Dp][Hp][Wp] (RSUPER_VOX_U8 / RSUPER_VOX_F32), of every plane the sub-box (z0, y0, x0) + (D, H, W) -> out [C][Do][Ho][Wo].
  * mode RSUPER_RESAMPLE_NEAREST: scale = (float)n_in / (float)n_out, src = min((int)floorf((float)dst * scale), n_in - 1) (F.interpolate 'nearest');
@@ -935,6 +939,32 @@ int rsuper_bspline_resample(const float* coef, int Z, int Y, int X, const int* i
  * source plane, overlapping buffers, C outside 1..65535 -> RSUPER_ERR_ARG. */
 int rsuper_reorient_store(const uint8_t* src, int C, int Z, int Y, int X, uint8_t* dst, long dst_bytes, long dst_offset, long plane_stride, int ni,
                           int nj, int nk, long ci, long cj, long ck, long coff, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * NIfTI CT + mask files -> a packed training case -- dataset_conversion/abdomenatlas_3d.py ResampleImage :59-103, process_case_bdmap_format :106,
+ * process_case_nnunet_format :150; dataset_conversion/nii2npz.py process_file :32-86.  csrc/nii_dataset.hip; the image goes through
+ * rsuper_nifti_load_prefilter / rsuper_bspline_resample / rsuper_ct_stats / rsuper_ct_normalize_pop.
+ * ------------------------------------------------------------------------------------------------ */
+#define RSUPER_LABEL_DESC_WORDS 8
+/* One output byte plane (up to eight classes) of a bit-packed label, gathered from the mask files' own voxel buffers.
+ * raw: device, raw_bytes bytes, 4-byte aligned: the voxel buffers of the group's files.  desc: device [nclass][RSUPER_LABEL_DESC_WORDS] int64, per class
+ * {element offset of its buffer in raw (in elements of its dtype), RSUPER_NII_* integer dtype (U8 .. I32), sz, sy, sx, base, elements of the buffer,
+ * absent}: canonical voxel (z, y, x) of the class is element base + z * sz + y * sy + x * sx of its buffer (nifti.canonical_layout; a flipped axis has
+ * a negative stride); absent != 0, an unknown or float dtype, a buffer that leaves raw or an element index outside the buffer read as 0.
+ * ix [Xb], iy [Yb], iz [Zb]: device int32, the nearest source index of every voxel of the resampled box on each axis (canonical source size Z, Y, X);
+ * an entry below 0 or at or above the axis is outside the scan.
+ * lut == NULL: 1 <= nclass <= 8, P == 1; dst [Do][Ho][Wo] u8 (any alignment) = OR_k (voxel of class k != 0) << (7 - k) inside the box
+ * (zo, yo, xo) + (Zb, Yb, Xb) and 0 in the padding around it: every byte of the plane is written, none beyond it, no memset is needed.
+ * lut != NULL (label-map mode): nclass == 1, lut device [n_values][P] u8, 1 <= P <= 8; dst [P][Do][Ho][Wo], byte of plane p = lut[value][p], a value
+ * below 0 or at or above n_values gives 0.  One launch.  Do * Ho * Wo < 2^31.  Null or misaligned pointers, non-positive sizes, a box outside the
+ * output, dst overlapping raw, nclass / P out of range -> RSUPER_ERR_ARG, checked before anything is launched. */
+int rsuper_label_gather_pack(const void* raw, long raw_bytes, const long long* desc, int nclass, const uint8_t* lut, int n_values, int P, const int* ix,
+                             const int* iy, const int* iz, int Z, int Y, int X, int Zb, int Yb, int Xb, uint8_t* dst, int Do, int Ho, int Wo, int zo, int yo,
+                             int xo, void* stream);
+/* packed: device [P][Do][Ho][Wo] u8 bit-packed (class c = bit 7 - (c & 7) of plane c >> 3), 1 <= P <= 8.  Inside the box (zo, yo, xo) + (Zb, Yb, Xb) the
+ * bit of class bg_class becomes (number of OTHER classes set at the voxel) != 1 -- nii2npz.py :58-60 (1 - sum) followed by the dataset's astype(bool):
+ * set where no class is and where two or more overlap.  Outside the box nothing is touched.  One launch. */
+int rsuper_label_background(uint8_t* packed, int P, int bg_class, int Do, int Ho, int Wo, int zo, int yo, int xo, int Zb, int Yb, int Xb, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,8 @@
 // ct_stats / ct_normalize: z-score of clip(x, lo, hi) with the whole-volume mean and unbiased standard deviation, written into a zero-padded output.
 //   launch 1  PARTS blocks; block b reduces its run of the volume in f64 and writes ONE partial (count, sum, sum of squares) into the caller's
 //             workspace.  Every block writes, an empty run writes zeros: the workspace needs no memset.
-//   launch 2  every block re-reduces the PARTS partials in the same fixed order, forms mean = S / N and std = sqrt((Q - N mean^2) / (N - 1)) in f64,
+//   launch 2  every block re-reduces the PARTS partials in the same fixed order, forms mean = S / N and std = sqrt((Q - N mean^2) / (N - 1)) in f64
+//             (rsuper_ct_normalize_pop: / N, the np.std of dataset_conversion/nii2npz.py :72),
 //             rounds each to f32 and writes (clip(x) - mean) / std (true division) inside the source box, 0 outside.
 //   No atomics, no host synchronisation between the two, the same bits on every run.  Squares of f32 values are exact in f64; with |clip(x)| <= 991 and
 //   N <= 3e8 the sum of squares stays below 2^49, and Q - N mean^2 loses fewer than 20 of the 53 bits.  Nothing is special-cased: a
@@ -102,6 +103,7 @@ struct NormArgs {
     int D, H, W, Do, Ho, Wo, z_lo, y_lo, x_lo;
     unsigned No, head, ngrp;                             // output voxels; scalar voxels before the first 16-byte boundary; 16-byte vectors
     float lo, hi;
+    int pop;                                             // divide the squared deviations by N (np.std, ddof = 0) instead of N - 1
 };
 
 // NORM: z-score with the statistics of the workspace; otherwise the box is copied as it is (pad_to_training_size on its own)
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(NT) void ct_normalize_kernel(NormArgs a) {
         cnt = shw[0][0]; sum = shw[0][1]; sq = shw[0][2];
         for (int w = 1; w < NT / 64; ++w) { cnt += shw[w][0]; sum += shw[w][1]; sq += shw[w][2]; }
         const double m = sum / cnt;
-        const double var = (sq - cnt * m * m) / (cnt - 1.0);          // unbiased; 0 / 0 and a negative rounding residue stay what they are
+        const double var = (sq - cnt * m * m) / (a.pop ? cnt : cnt - 1.0);   // unbiased unless pop; 0 / 0 and a negative rounding residue stay what they are
         mean = (float)m; sd = (float)sqrt(var);
         if (blockIdx.x == 0 && tid == 0) { a.ms[0] = mean; a.ms[1] = sd; }
     }
@@ -297,8 +299,9 @@ bool fits31(int a, int b, int c) { return (long)a * b * c < (1l << 31); }
 
 // launch 2 of the z-score, or the plain padded copy
 int pad_launch(bool norm, const void* x, int dtype, int D, int H, int W, float lo, float hi, const void* ws, float* out, int Do, int Ho, int Wo,
-               int z_lo, int y_lo, int x_lo, float* ms, void* stream) {
+               int z_lo, int y_lo, int x_lo, float* ms, void* stream, bool pop = false) {
     NormArgs a{};
+    a.pop = pop ? 1 : 0;
     a.x = x; a.out = out; a.ws = (const double*)ws; a.ms = ms;
     a.D = D; a.H = H; a.W = W; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.z_lo = z_lo; a.y_lo = y_lo; a.x_lo = x_lo;
     a.lo = lo; a.hi = hi;
@@ -354,6 +357,13 @@ int rsuper_ct_normalize(const void* x, int dtype, int D, int H, int W, float lo,
     if (!pad_args_ok(x, dtype, D, H, W, out, Do, Ho, Wo, z_lo, y_lo, x_lo) || !workspace || !mean_std) return RS_ERR_ARG;
     if (workspace_bytes < rsuper_ct_stats_workspace_bytes() || (uintptr_t)workspace % 8 || (uintptr_t)mean_std % 4) return RS_ERR_ARG;
     return pad_launch(true, x, dtype, D, H, W, lo, hi, workspace, out, Do, Ho, Wo, z_lo, y_lo, x_lo, mean_std, stream);
+}
+
+int rsuper_ct_normalize_pop(const void* x, int dtype, int D, int H, int W, float lo, float hi, const void* workspace, long workspace_bytes, float* out,
+                            int Do, int Ho, int Wo, int z_lo, int y_lo, int x_lo, float* mean_std, void* stream) {
+    if (!pad_args_ok(x, dtype, D, H, W, out, Do, Ho, Wo, z_lo, y_lo, x_lo) || !workspace || !mean_std) return RS_ERR_ARG;
+    if (workspace_bytes < rsuper_ct_stats_workspace_bytes() || (uintptr_t)workspace % 8 || (uintptr_t)mean_std % 4) return RS_ERR_ARG;
+    return pad_launch(true, x, dtype, D, H, W, lo, hi, workspace, out, Do, Ho, Wo, z_lo, y_lo, x_lo, mean_std, stream, true);
 }
 
 int rsuper_pad_box(const void* x, int dtype, int D, int H, int W, float* out, int Do, int Ho, int Wo, int z_lo, int y_lo, int x_lo, void* stream) {

@@ -172,6 +172,7 @@ _SIGS = {
     'rsuper_ct_stats_workspace_bytes': (c_long, []),
     'rsuper_ct_stats': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_long, P]),
     'rsuper_ct_normalize': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_long, P] + [c_int] * 6 + [P, P]),
+    'rsuper_ct_normalize_pop': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_long, P] + [c_int] * 6 + [P, P]),
     'rsuper_pad_box': (c_int, [P, c_int, c_int, c_int, c_int, P] + [c_int] * 6 + [P]),
     'rsuper_resample3d': (c_int, [P, c_int] + [c_int] * 10 + [P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     'rsuper_class_counts_workspace_bytes': (c_long, [c_int] * 5),
@@ -192,6 +193,8 @@ _SIGS = {
     'rsuper_nifti_load_prefilter': (c_int, [P, c_int, c_long, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_float, c_float, c_int, P, P]),
     'rsuper_bspline_resample': (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
     'rsuper_reorient_store': (c_int, [P, c_int, c_int, c_int, c_int, P, c_long, c_long, c_long, c_int, c_int, c_int, c_long, c_long, c_long, c_long, P]),
+    'rsuper_label_gather_pack': (c_int, [P, c_long, P, c_int, P, c_int, c_int, P, P, P] + [c_int] * 6 + [P] + [c_int] * 6 + [P]),
+    'rsuper_label_background': (c_int, [P] + [c_int] * 11 + [P]),
     'rsuper_grad_sqnorm':(c_int, [c_int, P, P, P, P]),
     'rsuper_clip_scale': (c_int, [c_int, P, P, c_float, P, P]),
     'rsuper_adamw_ema_step': (c_int, [c_int, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),

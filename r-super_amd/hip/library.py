@@ -57,6 +57,10 @@ NIfTI front and back end of a case (inference/nifti_device.py; no derivative):
     torch.ops.rsuper.nifti_load_prefilter(raw, dtype, size, strides, offset, slope, inter, prefilter) -> canonical (Z, Y, X) float32 samples / coefficients
     torch.ops.rsuper.bspline_resample(coef, ix, wx, iy, wy, iz, outside_value) -> (Zo, Yo, Xo) float32
     torch.ops.rsuper.reorient_store(stack, dst, dst_offset, plane_stride, shape_ijk, strides, offset)       (writes the planes into dst)
+NIfTI CT + mask files -> a packed training case (dataset_conversion/nii_dataset.py; no derivative):
+    torch.ops.rsuper.label_gather_pack(raw, desc, nclass, lut, ix, iy, iz, src_size, dst, plane, offset)    (writes one byte plane of dst, all with a lut)
+    torch.ops.rsuper.label_background(packed, bg_class, offset, box)                                        (sets the synthesised background bit)
+    torch.ops.rsuper.ct_normalize_pop(hu, lo, hi, out_shape, offset, workspace) -> ct_normalize with the population std (np.std)
 
 Only a "CUDA" kernel is registered: a CPU tensor reaches no kernel and raises (the product path has no CPU fallback).
 
@@ -315,3 +319,14 @@ def install_nifti_ops(load_prefilter, bspline_resample, reorient_store):
         ('bspline_resample', '(Tensor coef, Tensor ix, Tensor wx, Tensor iy, Tensor wy, Tensor iz, float outside_value) -> Tensor', bspline_resample),
         ('reorient_store', '(Tensor stack, Tensor(a!) dst, int dst_offset, int plane_stride, int[] shape_ijk, int[] strides, int offset) -> ()',
          reorient_store)))
+
+
+def install_nii_dataset_ops(label_gather_pack, label_background, ct_normalize_pop):
+    """The dataset-conversion operators of dataset_conversion/nii_dataset.py (at the end of that module's setup): packed label bits and a z-scored
+    image have no derivative."""
+    return _install_plain('nii_dataset', (
+        ('label_gather_pack', '(Tensor raw, Tensor desc, int nclass, Tensor? lut, Tensor ix, Tensor iy, Tensor iz, int[] src_size, Tensor(a!) dst, '
+         'int plane, int[] offset) -> ()', label_gather_pack),
+        ('label_background', '(Tensor(a!) packed, int bg_class, int[] offset, int[] box) -> ()', label_background),
+        ('ct_normalize_pop', '(Tensor hu, float lo, float hi, int[] out_shape, int[] offset, Tensor? workspace=None) -> (Tensor, Tensor)',
+         ct_normalize_pop)))

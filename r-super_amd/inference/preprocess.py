@@ -35,9 +35,10 @@ def _check_volume(hu, what):
     return hu.contiguous()
 
 
-def _ct_normalize_impl(hu, lo, hi, out_shape, offset, workspace=None):
+def _ct_normalize_impl(hu, lo, hi, out_shape, offset, workspace=None, pop=False):
     """hu (D, H, W) int16 / float32 -> ((Do, Ho, Wo) float32 with the z-score of clip(hu, lo, hi) at `offset` and zeros elsewhere, (mean, std) as a
-    2-element float32 device tensor).  Two launches, no host synchronisation."""
+    2-element float32 device tensor).  Two launches, no host synchronisation.  pop: the population std (rsuper_ct_normalize_pop: np.std, the
+    dataset conversion's) instead of the unbiased one."""
     hu = _check_volume(hu, 'ct_normalize')
     D, H, W = hu.shape
     Do, Ho, Wo = out_shape
@@ -48,8 +49,9 @@ def _ct_normalize_impl(hu, lo, hi, out_shape, offset, workspace=None):
     out = torch.empty((Do, Ho, Wo), device=hu.device, dtype=torch.float32)
     ms = torch.empty((2,), device=hu.device, dtype=torch.float32)
     _l.check(L.rsuper_ct_stats(hu.data_ptr(), _DT[hu.dtype], D, H, W, lo, hi, ws.data_ptr(), nbytes, _stream(hu)), 'ct_stats')
-    _l.check(L.rsuper_ct_normalize(hu.data_ptr(), _DT[hu.dtype], D, H, W, lo, hi, ws.data_ptr(), nbytes, out.data_ptr(), Do, Ho, Wo,
-                                   offset[0], offset[1], offset[2], ms.data_ptr(), _stream(hu)), 'ct_normalize')
+    _l.check((L.rsuper_ct_normalize_pop if pop else L.rsuper_ct_normalize)(hu.data_ptr(), _DT[hu.dtype], D, H, W, lo, hi, ws.data_ptr(), nbytes,
+                                                                           out.data_ptr(), Do, Ho, Wo, offset[0], offset[1], offset[2],
+                                                                           ms.data_ptr(), _stream(hu)), 'ct_normalize_pop' if pop else 'ct_normalize')
     return out, ms
 
 
