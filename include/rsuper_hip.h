@@ -626,6 +626,37 @@ int rsuper_lesion_candidates_run(float* work, uint8_t* out, int planes, int D, i
                                  void* workspace, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Lesion tables -- no counterpart in the reference: the connected components of masks[planes][D][H][W] (u8, non-zero = foreground; conn 6 or 26)
+ * as measured rows.  Components of fewer than min_voxels voxels are dropped; the others are ordered by voxel count descending, ties to the smaller
+ * root (the first voxel in C order), and the first max_lesions of a plane are its rows, row k with label k + 1.
+ *   totals[planes][4] i64   = { components kept after min_voxels, components dropped by it, foreground voxels, rows written }
+ *   rows_i[planes][max_lesions][16] i64 = { root, voxels, zmin, ymin, xmin, zmax, ymax, xmax, sum z, sum y, sum x, p3, q3, pa, qa, flags }
+ *   rows_f[planes][max_lesions][4] f64  = { d3, a, b, c } in mm between voxel centres (spacing s0, s1, s2 along D, H, W)
+ *   labels[planes][D][H][W] u8 (may be NULL) = 0 background, k + 1 a voxel of row k, 255 a voxel of a component without a row
+ * Rows past the last written one are zeroed.  d3: the largest distance between two voxels of the component, (p3, q3) the linear indices of the pair
+ * that attains it, p3 <= q3, the lexicographically smallest such pair (one voxel: d3 = 0, p3 = q3 = root).  a, (pa, qa): the same among pairs in one
+ * axis-0 slice, over all slices.  b: in the slice of (pa, qa), over the component's voxels v there, (max t_v - min t_v) / a with
+ * t_v = (dy s1)(x_v s2) - (dx s2)(y_v s1), (dy, dx) = qa - pa; 0 when a = 0.  c = (zmax - zmin) s0.  Squared distances are compared as
+ * (s0^2 dz^2 + s1^2 dy^2) + s2^2 dx^2 in f64, every product and sum rounded on its own.  The searches run over the voxels that have, along no axis
+ * (3-D) / along neither H nor W (in-slice), both neighbours in their own component: no other voxel can end an attaining pair.  A component with more
+ * than max_candidates such voxels for the 3-D search gets d3 = NaN, p3 = q3 = -1 and bit 0 of flags; its other fields stay exact.
+ * workspace: rsuper_lesion_table_workspace_bytes bytes on the device, 8-byte aligned like rows_i, rows_f and totals; it and the outputs may hold
+ * anything on entry.  rsuper_lesion_table_launches() kernels on `stream`, no memset, no device-to-host read.
+ * RSUPER_ERR_ARG, before anything is launched: null pointers (labels excepted), planes outside 1..RSUPER_LESION_MAX_PLANES, D*H*W > 2^31, conn other
+ * than 6 or 26, min_voxels < 1, max_lesions outside 1..RSUPER_LESION_TABLE_MAX_ROWS, max_candidates < 2, a spacing that is not finite and > 0,
+ * misaligned outputs, workspace_bytes below the requirement.  _workspace_bytes answers 0 for a shape it refuses. */
+#define RSUPER_LESION_TABLE_MAX_ROWS 254
+long rsuper_lesion_table_workspace_bytes(int planes, int D, int H, int W, int max_lesions);
+int rsuper_lesion_table_launches(void);
+int rsuper_lesion_table(const uint8_t* masks, int planes, int D, int H, int W, int conn, int min_voxels, int max_lesions, int max_candidates, double s0,
+                        double s1, double s2, long long* rows_i, double* rows_f, long long* totals, uint8_t* labels, void* workspace,
+                        long workspace_bytes, void* stream);
+/* Joint histogram of two label volumes [planes][voxels] u8 with values 0..Ka and 0..Kb (each at most RSUPER_LESION_TABLE_MAX_ROWS):
+ * counts[planes][Ka + 1][Kb + 1] i64 (8-byte aligned, any content on entry).  A voxel whose value is above Ka / Kb on either side (255 among them)
+ * counts nowhere; counts[.][0][0] stays 0 -- voxels that are background on both sides are skipped.  Two launches, integer atomics. */
+int rsuper_label_overlap(const uint8_t* labels_a, const uint8_t* labels_b, int planes, long voxels, int Ka, int Kb, long long* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Validation metrics -- metric/metrics.py compute_surface_distances :265-573.  Masks of up to 2^31 corners ((D+1) * (H+1) * (W+1)).
  * No call issues a memset: counters and bounds are initialised by the call's own kernels.
  * ------------------------------------------------------------------------------------------------ */

@@ -146,6 +146,10 @@ _SIGS = {
     'rsuper_lesion_candidates_workspace_bytes': (c_long, [c_int] * 4),
     'rsuper_lesion_candidates_begin': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     'rsuper_lesion_candidates_run': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, c_int, c_float, P, P, c_int, P]),
+    'rsuper_lesion_table_workspace_bytes': (c_long, [c_int] * 5),
+    'rsuper_lesion_table_launches': (c_int, []),
+    'rsuper_lesion_table': (c_int, [P] + [c_int] * 8 + [c_double] * 3 + [P, P, P, P, P, c_long, P]),
+    'rsuper_label_overlap': (c_int, [P, P, c_int, c_long, c_int, c_int, P, P]),
     'rsuper_affine_crop': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),
     'rsuper_intensity_augment_workspace_bytes': (c_long, [c_int] * 4),
     'rsuper_intensity_augment_launches': (c_int, [c_int, P]),

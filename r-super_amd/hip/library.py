@@ -51,6 +51,9 @@ whole-case preprocessing and resampling (inference/preprocess.py, inference/resa
     torch.ops.rsuper.resample3d(x, box, out_size, interp, threshold) -> resampled class stack
 report-guided pseudo-label refinement (baselines/pseudo_labels/pseudo_label_report_refinement.py; no derivative):
     torch.ops.rsuper.lesion_candidates(prob, n_lesions, peak_cut, min_voxels, min_peak, batch) -> (uint8 masks, per-plane state words)
+lesion tables (inference/lesions.py; no derivative):
+    torch.ops.rsuper.lesion_table(masks, spacing, conn, min_voxels, max_lesions, max_candidates, return_labels) -> (rows_i, rows_f, totals, labels)
+    torch.ops.rsuper.label_overlap(labels_a, labels_b, Ka, Kb) -> joint histogram of two label stacks
 compressed mask files (inference/npz_writer.py; no derivative):
     torch.ops.rsuper.deflate_planes(src, n, plane_stride, planes, pitch, table, header, header_bits) -> (streams back to back, offsets / sizes / CRCs)
 NIfTI front and back end of a case (inference/nifti_device.py; no derivative):
@@ -301,6 +304,15 @@ def install_pseudo_label_ops(lesion_candidates):
     return _install_plain('pseudo_label', (
         ('lesion_candidates', '(Tensor prob, int[] n_lesions, float peak_cut, int min_voxels, float min_peak, int batch) -> (Tensor mask, Tensor state)',
          lesion_candidates),))[0]
+
+
+def install_lesion_ops(lesion_table, label_overlap):
+    """The lesion-table operators of inference/lesions.py (at the end of that module's setup): integer tables, measured sizes and label volumes have
+    no derivative."""
+    return _install_plain('lesions', (
+        ('lesion_table', '(Tensor masks, float[] spacing, int conn, int min_voxels, int max_lesions, int max_candidates, bool return_labels) '
+         '-> (Tensor rows_i, Tensor rows_f, Tensor totals, Tensor labels)', lesion_table),
+        ('label_overlap', '(Tensor labels_a, Tensor labels_b, int Ka, int Kb) -> Tensor', label_overlap)))
 
 
 def install_deflate_ops(deflate_planes):

@@ -12,3 +12,5 @@ from .scoring import score_case  # noqa: F401
 from .npz_writer import deflate_device, savez_compressed_device, save_planes_npz, gzip_device  # noqa: F401
 from .nifti import read_nifti, affine, orientation_plan, nifti1_header, resample_axis_table  # noqa: F401
 from .nifti_device import load_nifti_device, predict_nifti_case, save_nifti_masks  # noqa: F401
+from .lesions import (LesionTable, lesion_table, match_lesions, locate_lesions, lesion_report_rows, compare_with_report,  # noqa: F401
+                      lesion_csv_rows)

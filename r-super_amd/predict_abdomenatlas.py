@@ -20,6 +20,10 @@ Outputs under `<save_path>/<dataset>/<folder of the first checkpoint>/<case>/`:
 the same files, keys and arrays under np.load, other compressed bytes.  Without it every byte written is np.savez_compressed's.  The float32
 probabilities stay on the host path.
 
+--lesion_table measures the lesions of every saved lesion class while the masks are still on the device (inference.lesion_table: count, voxels, extent,
+diameters; --lesion_min_voxels drops smaller components) and appends one row per lesion to <save_path>/lesions.csv, with the organ sub-segment it
+sits in when planes named '<organ>_...' are among the classes.  Without the flag not one byte of output changes.
+
 --score measures every case while it is still on the device (inference.score_case) and appends the rows to tumor_detection_results.csv and, with
 probabilities, tumor_detection_results_th0.1.csv ... in the save path; with --not_save_binary nothing has to be written and read back.
 
@@ -74,6 +78,9 @@ def get_parser(argv=None, config_root=None):
     p.add_argument('--nifti', action='store_true', help='accept <id>.nii.gz and <id>/ct.nii.gz cases: read, reorient and resample them on the device and '
                    'save the masks as .nii.gz on the scan\'s own grid (ignored for .npz / .npy cases)')
     p.add_argument('--th', type=float, default=0.5, help='threshold that binarises a mask for --score')
+    p.add_argument('--lesion_table', action='store_true', help='measure the predicted lesions of every saved lesion class on the device and append '
+                   'them to <save_path>/lesions.csv (inference/lesions.py)')
+    p.add_argument('--lesion_min_voxels', type=int, default=1, help='components below this many voxels are no lesions for --lesion_table')
     args = p.parse_args(argv)
     path = args.config
     if path is None:
@@ -277,6 +284,24 @@ def write_raw(case_dir, raw_dict, names):
         _save_nifti_copy(host[k], os.path.join(case_dir, 'predictions_raw', n + '.nii.gz'))
 
 
+def measure_lesions(pred_dict, class_list, names, spacing, case_id, min_voxels=1):
+    """The lesions.csv rows of one case: one inference.lesion_table call over the lesion planes of `names` (mask > 0), and per lesion class with
+    sub-segment planes in pred_dict one locate_lesions call."""
+    from .inference.lesions import lesion_csv_rows, lesion_table, locate_lesions, segment_classes
+    lesions = [n for n in names if 'lesion' in n]
+    if not lesions:
+        return []
+    table = lesion_table(torch.stack([(pred_dict[n] > 0).to(torch.uint8) for n in lesions]), spacing=spacing, min_voxels=min_voxels, return_labels=True)
+    rows = []
+    for p, n in enumerate(lesions):
+        segs = [c for c in segment_classes(n, class_list) if c in pred_dict]
+        loc = None
+        if segs and table.count(p):
+            loc = locate_lesions(table.plane(p), torch.stack([pred_dict[c] > 0 for c in segs]), segs)
+        rows += lesion_csv_rows(table, case_id, n, loc, plane=p)
+    return rows
+
+
 def main(argv=None, config_root=None):
     """Returns the list of predicted case ids and the seconds per stage {'read', 'predict', 'postprocess', 'measure', 'write'}."""
     import yaml
@@ -337,6 +362,7 @@ def main(argv=None, config_root=None):
                 pred_dict, raw = predict_one(models, hu, pancreas, args, class_list)
             t = clock('predict', t)
             raw_dict = postprocess_npz(raw, class_list, args) if want_raw else None
+            all_planes = pred_dict
             pred_dict = {n: pred_dict[n] for n in names}
             if raw_dict is not None:
                 raw_dict = {n: raw_dict[n] for n in names}
@@ -346,6 +372,12 @@ def main(argv=None, config_root=None):
                 row, rows = score_case(pred_dict, raw_dict, names, spacings.get(case_id, (1.0, 1.0, 1.0) if geom is None else geom.spacing[::-1]),
                                        th=args.th, case_id=case_id)
                 append_rows(args.save_path, row, rows)
+                t = clock('measure', t)
+            if args.lesion_table:
+                from .inference.lesions import append_csv
+                append_csv(os.path.join(args.save_path, 'lesions.csv'),
+                           measure_lesions(all_planes, class_list, names, spacings.get(case_id, (1.0, 1.0, 1.0) if geom is None else geom.spacing[::-1]),
+                                           case_id, args.lesion_min_voxels))
                 t = clock('measure', t)
             if not args.not_save_binary or want_raw:
                 os.makedirs(case_dir, exist_ok=True)
