@@ -146,6 +146,24 @@ __device__ __forceinline__ void row_to_hw(int i, int& hs, int& w) {
     else if (i < 28) { hs = 0; w = i - 12; }
     else { hs = 1; w = i - 16; }
 }
+// row_to_hw without branches: inside the persistent kernels the if-chain becomes a private-memory lookup table (scratch) otherwise
+__device__ __forceinline__ void row_to_hw_nt(int i, int& hs, int& w) {
+    hs = (int)((0xF00F0FF0u >> i) & 1u);
+    const unsigned long long t = i < 16 ? 0x7654765432103210ull : 0xFEDCFEDCBA98BA98ull;
+    w = (int)((t >> ((i & 15) * 4)) & 15ull);
+}
+
+// Descriptor of one output tile of the persistent igemm kernels (conv3d_igemm_kd / _s2k / _s2d.hip), wave-uniform: halo origin voxel, two words of
+// "outside the volume" bits of the halo coordinates (layout: at each kernel's table fill), d0 | h0 << 10 | w0 << 20
+struct Tile { uint32_t base, bad0, bad1, org; };
+
+// Raw sources need no arithmetic on their way into LDS: `buffer_load_dwordx4 ... lds` copies 1 KB per wave instruction from per-lane global offsets
+// (voff, plus the wave-uniform soff) into a lane-linear LDS image (lane l -> M0 + 16 l), out-of-range offsets arrive as zeros (semantics pinned by
+// tools/ubench/lds_dma_probe.hip).  The compiler does not see the instruction: completion is waited for by an explicit counted vmcnt before the barrier
+// that publishes the buffer.  (conv3d_wgrad2.hip keeps its own form without the scalar offset operand.)
+__device__ __forceinline__ void lds_dma16(const __amdgpu_buffer_rsrc_t& rs, uint32_t voff, uint32_t soff, uint32_t lds_byte) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds" : : "v"(voff), "s"(lds_byte), "s"(rs), "s"(soff) : "memory", "m0");
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

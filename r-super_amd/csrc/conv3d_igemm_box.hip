@@ -20,9 +20,6 @@
 // per voxel ACROSS row and plane boundaries, so any 16 consecutive flat rows (one ds_read_b128 lane group) hit 16 distinct
 // 16-byte bank groups -- conflict-free for every box shape.
 #include <type_traits>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -45,12 +42,6 @@ template <int TD_, int TH_, int TW_> struct Box {
 };
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-#ifdef RS_BOX_PROF
-__device__ unsigned long long g_box_prof[64 * 32];        // [block slot][stamp]
-#define BOX_STAMP(k) do { if (lane == 0 && wave == 0 && blockIdx.x % 16 == 0 && blockIdx.x / 16 < 64) g_box_prof[(blockIdx.x / 16) * 32 + (k)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define BOX_STAMP(k)
-#endif
 
 // EPI: 0 forward (optional residual, statistics of the output), 1 data gradient (ReLU mask, InstanceNorm-backward sums)
 // SPLIT: the block handles the chunk range [cb, cb + nk) of split blockIdx-derived `sp` and writes the raw f32 tile to the workspace
@@ -88,7 +79,6 @@ __global__ __launch_bounds__(256, 2) void igemm_box_kernel(IgemmParams p, int bd
     const int th = t % bh; t /= bh;
     const int d0 = t * B::TD, h0 = th * B::TH, w0 = tw * B::TW;
 
-    BOX_STAMP(0);
     const int nchA = (p.a.C + KC - 1) / KC, nchB = (p.b.C + KC - 1) / KC;
     const int nch = nchA + nchB;
     const int cper = SPLIT ? (nch + p.nsplit - 1) / p.nsplit : nch;      // chunks per split
@@ -272,9 +262,7 @@ __global__ __launch_bounds__(256, 2) void igemm_box_kernel(IgemmParams p, int bd
         for (int nf = 0; nf < NFR; ++nf)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mf][nf][r] = 0.f;
-    BOX_STAMP(1);
     if (hsel == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
-    BOX_STAMP(2);
 
     // ------------------------------------------------------------------ K-partial reduction fused into the epilogue
     // Per group of GM row fragments: every wave writes ITS partial sums voxel-major as f32 ([wave][flat row][BN] + 16 B pad),
@@ -385,7 +373,6 @@ __global__ __launch_bounds__(256, 2) void igemm_box_kernel(IgemmParams p, int bd
             }
         }
     }
-    BOX_STAMP(4);
     if (p.part && !SPLIT) {
         __syncthreads();
         float* red = (float*)smem;                           // [RPT][BN][2]
@@ -405,7 +392,6 @@ __global__ __launch_bounds__(256, 2) void igemm_box_kernel(IgemmParams p, int bd
             }
         }
     }
-    BOX_STAMP(5);
 }
 
 // Second pass of the cross-block split: out = epilogue(sum over the splits of ws[s][voxel][Cout]).  Block = 32 voxels x 64 columns
@@ -497,20 +483,6 @@ int launch_box(const IgemmParams& p, int epi, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         hipLaunchKernelGGL(k, grid, block, smem, st, p, bd, bh, bw);
     }
-#ifdef RS_BOX_PROF
-    if (getenv("RSUPER_BOX_PROF")) {
-        static unsigned long long h[64 * 32];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_box_prof), sizeof(h));
-        for (int b = 0; b < 64; b += 3) {
-            if (!h[b * 32]) continue;
-            fprintf(stderr, "box_prof blk %4d: prologue %6llu main %7llu epi %6llu stats %6llu | total %7llu\n", b * 16,
-                    h[b * 32 + 1] - h[b * 32], h[b * 32 + 2] - h[b * 32 + 1], h[b * 32 + 4] - h[b * 32 + 2], h[b * 32 + 5] - h[b * 32 + 4], h[b * 32 + 5] - h[b * 32]);
-        }
-        memset(h, 0, sizeof(h));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_box_prof), h, sizeof(h));
-    }
-#endif
     if (SPLIT) {
         const int vox_s = p.D * p.H * p.W;
         dim3 g2((unsigned)((vox_s + 31) / 32), (unsigned)((p.Cout + 63) / 64), (unsigned)p.N);

@@ -22,8 +22,6 @@
 //     tile's last MFMA loop, statistics reduced per tile into per-wave LDS accumulators (one partial row per (block, h pair)).
 #include "common.hpp"
 #include "kernels.hpp"
-#include <stdlib.h>
-#include <stdio.h>
 #include <type_traits>
 
 namespace {
@@ -39,27 +37,8 @@ constexpr int SCR_ROW = 36;                         // floats per epilogue scrat
 constexpr int SCR_BYTES = 32 * SCR_ROW * 4;         // per wave
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
-// raw sources need no arithmetic on their way into LDS: `buffer_load_dwordx4 ... lds` copies 1 KB per wave instruction from per-lane global offsets into a
-// lane-linear LDS image (lane l -> M0 + 16 l), out-of-range offsets arrive as zeros (semantics pinned by tools/ubench/lds_dma_probe.hip, as in
-// conv3d_wgrad2.hip).  The compiler does not see the instruction: completion is waited for by an explicit counted vmcnt before the item barrier.
-__device__ __forceinline__ void kd_dma16(const __amdgpu_buffer_rsrc_t& rs, uint32_t voff, uint32_t soff, uint32_t lds_byte) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds" : : "v"(voff), "s"(lds_byte), "s"(rs), "s"(soff) : "memory", "m0");
-}
-
-// row_to_hw (common.hpp) without branches: the if-chain becomes a private-memory lookup table (scratch) otherwise
-__device__ __forceinline__ void row_to_hw_nt(int i, int& hs, int& w) {
-    hs = (int)((0xF00F0FF0u >> i) & 1u);
-    const unsigned long long t = i < 16 ? 0x7654765432103210ull : 0xFEDCFEDCBA98BA98ull;
-    w = (int)((t >> ((i & 15) * 4)) & 15ull);
-}
-
-#ifdef KD_PROF
-__device__ unsigned long long g_kd_prof[8 * 4 + 2];                // block (0, 0, 0): [wave][item-loop, barrier, epilogue ticks, items], kernel ticks, 100 MHz ticks
-#endif
-
 // one 16-channel slice of [a | b]: first channel, channels / row bytes / base / bytes of its source, table index of its constants, byte offset of its packed weights (tap 0)
 struct Item { int c, C; uint32_t rowb, nrec; uint64_t base; int tabc; uint32_t wofs; };
-struct Tile { uint32_t base, bad0, bad1, org; };
 
 // NF0 / NF1: 32-column fragments of the waves 0-3 / 4-7 (block = (NF0 + NF1) x 32 columns).  EPI: 0 forward, 1 data gradient, 2 forward + residual.
 // NORM: both sources carry (mean, rstd) and are staged through registers; raw sources are staged by LDS-DMA.
@@ -67,12 +46,9 @@ template <int NF0, int NF1, int EPI, bool NORM>
 __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BN32 = NF0 + NF1;
-#ifndef KD_DMA
-#define KD_DMA 1
-#endif
     // raw sources: LDS-DMA for the wide blocks (no registers to spare there); 64-column blocks stage through registers like the normalised ones -- with the
     // DMA pieces in the VMEM queue every wait for a weight fragment issued after them also waits for the pieces (in-order vmcnt): item loop 4.4 k -> 6.8 k ticks
-    constexpr bool DMA = !NORM && (KD_DMA == 2 || (KD_DMA == 1 && BN32 > 2));
+    constexpr bool DMA = !NORM && BN32 > 2;
     // Every field is copied into a local once, and selections between the two sources are mask arithmetic further down: inside by-reference lambdas a
     // `cond ? b : a` of two such variables becomes a select of two ADDRESSES -- the variables then live in scratch, every use is a flat load + vmcnt(0) and
     // everything derived from it a per-lane value (waterfall loops around the buffer instructions).  Measured: 938 us vs 559 us on up4.0 forward.
@@ -270,17 +246,15 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
                 ok = ok && (((t.bad0 >> hd) | (t.bad0 >> (6 + hh)) | (t.bad1 >> hw)) & 1u) == 0u;
             }
             const uint32_t voff = ok ? __umul24(t.base + (q & 0xFFFFFFu), it.rowb) + slot * 16u : 0xFFFFFFF0u;
-            kd_dma16(rs, voff, (uint32_t)(it.c * 2), lbase + (uint32_t)k * 8192u);
+            lds_dma16(rs, voff, (uint32_t)(it.c * 2), lbase + (uint32_t)k * 8192u);
         }
     };
 
     auto run = [&](auto NF_, auto LATE_) {
         constexpr int NF = std::remove_reference_t<decltype(NF_)>::value;
         constexpr bool late = std::remove_reference_t<decltype(LATE_)>::value;
-#ifndef KD_RB
-#define KD_RB 3
-#endif
-        constexpr int RB = NF == 1 ? KD_RB : 2;                                        // weight ring, in (kh, kw) groups: 3 divides the 9 groups of an item, 2 needs a move per item
+        constexpr int KD_RB = 3;
+        constexpr int RB = NF == 1 ? KD_RB : 2;                          // weight ring, in (kh, kw) groups: 3 divides the 9 groups of an item, 2 needs a move per item
         constexpr int EVF = NF == 1 ? 2 : 1;                             // fragments whose epilogue operands are requested ahead (2 vectors each)
         const int ntile0 = blockIdx.y * BN32 + (nhalf ? NF0 : 0);
         // A fragments: lane -> (row of the h pair, w) by row_to_hw, 16-byte half lane >> 5
@@ -376,19 +350,9 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
 
         int kc = 0, jc = 0;                                              // (tile, slice) of the current item
         Tile tc = fetch_tile(0);
-#ifndef KD_PRIO
-#define KD_PRIO 5
-#endif
-        if (KD_PRIO == 1 && !late) __builtin_amdgcn_s_setprio(1);        // measured: priority only swaps which wave of a SIMD runs ahead (tools/kd_prof.sh)
-#ifdef KD_PROF
-        unsigned long long pf_loop = 0, pf_bar = 0, pf_epi = 0;
-        const unsigned long long pf_c0 = __builtin_readcyclecounter(), pf_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+        constexpr int KD_PRIO = 5;                                       // 1: one fixed priority for the early wave of a SIMD; 4, 5: by progress through the item (below)
+        if (KD_PRIO == 1 && !late) __builtin_amdgcn_s_setprio(1);        // measured: a fixed priority only swaps which wave of a SIMD runs ahead
         for (int it = 0; it < nitems; ++it) {
-#ifdef KD_PROF
-            const unsigned long long q0 = __builtin_readcyclecounter();
-            unsigned long long q1 = q0;
-#endif
             const char* buf = bufs + (it & 1) * HB;
             char* nxt = bufs + ((it + 1) & 1) * HB;
             const bool last = jc == nk - 1;                              // this item completes a tile
@@ -400,9 +364,7 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
             Item i2 = i1;
             const uint32_t wofs_next = i1.wofs;                          // weights of the next item: the ring runs across the barrier
             if constexpr (DMA) {
-#ifndef KD_SKIP_STAGE
                 dma_item(t1, i1, (uint32_t)((it + 1) & 1) * HB);
-#endif
             } else {
                 if (j2 == 0) t2 = fetch_tile(k2);
                 i2 = item_of(j2);
@@ -435,10 +397,8 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
                     ev[f % EVF][ps] = *(const uint4*)ptr;
                 }
             };
-#ifndef KD_AD
-#define KD_AD 5
-#endif
-            constexpr int AD = NF == 1 ? ((EPI != 0 && NORM) ? KD_AD - 2 : KD_AD) : 2, AR = AD + 1;   // (residual / mask operands in flight: fewer fragments ahead, no spill)                       // fragment ring / prefetch distance
+            constexpr int KD_AD = 5;
+            constexpr int AD = NF == 1 ? ((EPI != 0 && NORM) ? KD_AD - 2 : KD_AD) : 2, AR = AD + 1;   // fragment ring / prefetch distance (residual / mask operands in flight: fewer fragments ahead, no spill)
             uint4 aq[AR];
             if (!wave_live) {                                            // a dead wave only stages its share (register path) and meets the others at the barrier
                 if constexpr (!DMA) {
@@ -472,16 +432,12 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
 #pragma unroll
                 for (int dp = 0; dp < HD; ++dp) {
                     const int s = g * HD + dp;
-#ifndef KD_SKIP_A
                     if (s + AD < 9 * HD) aq[(s + AD) % AR] = fetch_a((s + AD) / HD, (s + AD) % HD);
-#endif
-#ifndef KD_SKIP_B
                     if (dp < 3) {                                        // weights of group g + RB - 1 (possibly of the next item), tap kd = dp
                         const int gn = g + RB - 1;
                         if (gn < 9) load_b(wofs_cur, gn, dp, bq[gn % RB][dp]);
                         else load_b(wofs_next, gn - 9, dp, bq[gn % RB][dp]);
                     }
-#endif
                     if (EPI != 0) {
 #pragma unroll
                         for (int f = 0; f < EVF; ++f)
@@ -493,16 +449,8 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
                         const int d = dp - kd;
                         if (d < 0 || d >= TD) continue;
 #pragma unroll
-                        for (int nf = 0; nf < NF; ++nf) {
-#ifndef KD_SKIP_MMA
-                            mma32<bf16_t>(acc[d][nf], aq[s % AR], bq[g % RB][kd][nf]);
-#else
-                            if (s == 0) mma32<bf16_t>(acc[d][nf], aq[s % AR], bq[g % RB][kd][nf]);
-                            else asm volatile("" : : "v"(aq[s % AR]), "v"(bq[g % RB][kd][nf]));
-#endif
-                        }
+                        for (int nf = 0; nf < NF; ++nf) mma32<bf16_t>(acc[d][nf], aq[s % AR], bq[g % RB][kd][nf]);
                     }
-#ifndef KD_SKIP_STAGE                                                    // ablation switches (tools/kd_ablate.sh): where the time of an item goes
                     if constexpr (!DMA) {
                         // hooks: 25 pieces per item (4 words + store / next load per vector) spread over the 54 steps; the two waves of a SIMD one step apart
 #pragma unroll
@@ -516,7 +464,6 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
                                 }
                             }
                     }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -526,14 +473,7 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
 #pragma unroll
                     for (int nf = 0; nf < NF; ++nf) bq[0][kd][nf] = bq[1][kd][nf];
             }
-#ifdef KD_PROF
-            q1 = __builtin_readcyclecounter();
-#endif
-#ifdef KD_SKIP_EPI
-            if (last && it == nitems - 1) {
-#else
             if (last) {
-#endif
                 // -------------------------------------------------------------- wave-private epilogue of this tile
                 const int hi = lane >> 5, col_l = lane & 31;
 #pragma unroll
@@ -619,9 +559,6 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
                 }
             }
         item_done:
-#ifdef KD_PROF
-            const unsigned long long q2 = __builtin_readcyclecounter();
-#endif
             if constexpr (DMA) {
                 // this item's DMA pieces were its first VMEM operations: at most the weight fragments requested for the next item may still be in flight
                 // (a tile's last item also issued the epilogue's stores after them: drain)
@@ -629,10 +566,6 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
                 else asm volatile("s_waitcnt vmcnt(%0)" : : "n"((RB - 1) * 3 * NF) : "memory");
             }
             __syncthreads();                                             // item it consumed, item it + 1 complete in the other buffer
-#ifdef KD_PROF
-            const unsigned long long q3 = __builtin_readcyclecounter();
-            pf_loop += q1 - q0; pf_epi += q2 - q1; pf_bar += q3 - q2;
-#endif
             // advance the item cursors
             if (++jc == nk) { jc = 0; ++kc; tc = fetch_tile(kc); }
             wofs_cur = wofs_next;
@@ -642,12 +575,6 @@ __global__ __launch_bounds__(NT, 2) void igemm_kd_kernel(IgemmParams p) {
             } else { t1 = t2; i1 = i2; }
             k1 = k2; j1 = j2;
         }
-#ifdef KD_PROF
-        if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0) {
-            g_kd_prof[wave * 4] = pf_loop; g_kd_prof[wave * 4 + 1] = pf_bar; g_kd_prof[wave * 4 + 2] = pf_epi; g_kd_prof[wave * 4 + 3] = (unsigned long long)nitems;
-            if (wave == 0) { g_kd_prof[32] = __builtin_readcyclecounter() - pf_c0; g_kd_prof[33] = __builtin_amdgcn_s_memrealtime() - pf_r0; }
-        }
-#endif
         // statistics: ONE partial row per (block, h pair); this wave's columns
         if (RSTAT && partp) {
 #pragma unroll
@@ -718,16 +645,6 @@ int launch_kd(const IgemmParams& p, int epi, hipStream_t st) {
         else KD_LAUNCH(0, false)
     }
 #undef KD_LAUNCH
-#ifdef KD_PROF
-    if (getenv("RSUPER_KD_PROF")) {
-        unsigned long long h[34];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_kd_prof), sizeof(h));
-        fprintf(stderr, "kd_prof epi%d norm%d bn%d (ticks per item):", epi, (int)norm, p.bn);
-        for (int w = 0; w < 8; ++w) fprintf(stderr, " w%d loop %.0f epi %.0f bar %.0f |", w, (double)h[w * 4] / h[w * 4 + 3], (double)h[w * 4 + 2] / h[w * 4 + 3], (double)h[w * 4 + 1] / h[w * 4 + 3]);
-        fprintf(stderr, " items %llu; %llu ticks in %.1f us (100 MHz counter) = %.0f MHz\n", h[3], h[32], h[33] / 100.0, h[32] / (h[33] / 100.0));
-    }
-#endif
     return rs_check_launch();
 }
 

@@ -26,9 +26,6 @@
 #include "common.hpp"
 #include "kernels.hpp"
 
-#ifndef S2_SKIP
-#define S2_SKIP 0
-#endif
 namespace {
 
 constexpr int TH = 4, TW = 16;
@@ -213,21 +210,19 @@ __global__ __launch_bounds__(256, 1) void igemm_s2_kernel(IgemmParams p, int FD,
     auto item = [&](auto clsc, int ch, const uint4* wch) __attribute__((always_inline)) {
         constexpr int CLS = decltype(clsc)::value;
         __syncthreads();                                                        // previous item consumed (and mr_lds visible)
-        if (!(S2_SKIP & 4)) commit(ch);
+        commit(ch);
         __syncthreads();
         if constexpr (CLS < 7) {
-            if (!(S2_SKIP & 4)) stage(ch, CLS + 1);
+            stage(ch, CLS + 1);
             if constexpr (CLS & 1) load_b(std::integral_constant<int, (CLS + 1) & 7>{}, wch, fbqA);
             else load_b(std::integral_constant<int, (CLS + 1) & 7>{}, wch, fbqB);
         } else if (ch + 1 < nch) {
-            if (!(S2_SKIP & 4)) stage(ch + 1, 0);
+            stage(ch + 1, 0);
             load_b(std::integral_constant<int, 0>{}, wch + (size_t)27 * 2 * wstep, fbqA);
         }
         __builtin_amdgcn_sched_barrier(0);                                      // the requests stay ahead of this item's MFMAs
-        if (!(S2_SKIP & 2)) {
-            if constexpr (CLS & 1) mfma_class(clsc, fbqB);
-            else mfma_class(clsc, fbqA);
-        }
+        if constexpr (CLS & 1) mfma_class(clsc, fbqB);
+        else mfma_class(clsc, fbqA);
         __builtin_amdgcn_sched_barrier(0);
     };
 
@@ -283,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void igemm_s2_kernel(IgemmParams p, int FD,
         const uint4* wch = wp + (size_t)ch * 27 * 2 * wstep + (size_t)ntile0 * 64 + lane;
         if constexpr (MODE == 1) {
             if (ch == 0) {
-                if (!(S2_SKIP & 4)) stage(0, 0);
+                stage(0, 0);
                 load_b(std::integral_constant<int, 0>{}, wch, fbqA);
             }
             item(std::integral_constant<int, 0>{}, ch, wch); item(std::integral_constant<int, 1>{}, ch, wch);
@@ -291,12 +286,12 @@ __global__ __launch_bounds__(256, 1) void igemm_s2_kernel(IgemmParams p, int FD,
             item(std::integral_constant<int, 4>{}, ch, wch); item(std::integral_constant<int, 5>{}, ch, wch);
             item(std::integral_constant<int, 6>{}, ch, wch); item(std::integral_constant<int, 7>{}, ch, wch);
         } else {
-            if (!(S2_SKIP & 4)) { if (ch == 0) stage(0, 0); }
+            if (ch == 0) stage(0, 0);
             __syncthreads();
-            if (!(S2_SKIP & 4)) commit(ch);
+            commit(ch);
             __syncthreads();
-            if (!(S2_SKIP & 4)) { if (ch + 1 < nch) stage(ch + 1, 0); }         // the next chunk's loads fly during this chunk's MFMAs
-            if (!(S2_SKIP & 2)) mfma_all(wch);
+            if (ch + 1 < nch) stage(ch + 1, 0);                                 // the next chunk's loads fly during this chunk's MFMAs
+            mfma_all(wch);
         }
     }
 
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(256, 1) void igemm_s2_kernel(IgemmParams p, int FD,
     for (int j = 0; j < KP; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
     const int LD = MODE == 2 ? FD : p.D, LH = MODE == 2 ? FH : p.H, LW = MODE == 2 ? FW : p.W;      // grid of the stores
 #pragma unroll
-    for (int c = 0; c < ((S2_SKIP & 1) ? 1 : NACC); ++c) {
+    for (int c = 0; c < NACC; ++c) {
         const int od = (c >> 2) & 1, oh = (c >> 1) & 1, ow = c & 1;
 #pragma unroll
         for (int q = 0; q < NPASS; ++q) {

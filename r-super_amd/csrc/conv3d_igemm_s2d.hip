@@ -35,17 +35,7 @@ constexpr int NT = 512, NW = 8;
 constexpr int SCR_ROW = 36, SCR_BYTES = 32 * SCR_ROW * 4;
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void s2d_dma16(const __amdgpu_buffer_rsrc_t& rs, uint32_t voff, uint32_t soff, uint32_t lds_byte) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds" : : "v"(voff), "s"(lds_byte), "s"(rs), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ void row_to_hw_nt(int i, int& hs, int& w) {
-    hs = (int)((0xF00F0FF0u >> i) & 1u);
-    const unsigned long long t = i < 16 ? 0x7654765432103210ull : 0xFEDCFEDCBA98BA98ull;
-    w = (int)((t >> ((i & 15) * 4)) & 15ull);
-}
-
 struct Item { int c, C; uint32_t rowb, nrec; uint64_t base; uint32_t wofs; };
-struct Tile { uint32_t base, bad0, bad1, org; };
 
 // the 27 (offset, class, weight fragment) triples in issue order: offsets 0..7 (bit per axis: 0 -> dy[q], 1 -> dy[q + 1]); per axis an offset bit 0 serves
 // class bit 0 with fragment 1 and class bit 1 with fragment 0, an offset bit 1 serves class bit 1 with fragment 2 (fragment = 2 - tap: flipped packing)
@@ -197,9 +187,9 @@ __global__ __launch_bounds__(NT, 2) void igemm_s2d_kernel(IgemmParams p, int FD,
                     ok = ok && (((t.bad0 >> hd) | (t.bad0 >> (5 + hh)) | (t.bad1 >> hw)) & 1u) == 0u;
                 }
                 const uint32_t voff = ok ? __umul24(t.base + (v & 0xFFFFFFu), it.rowb) + slot * 16u : 0xFFFFFFF0u;
-                s2d_dma16(rs, voff, (uint32_t)(it.c * 2), lbase + (uint32_t)k * 8192u);
+                lds_dma16(rs, voff, (uint32_t)(it.c * 2), lbase + (uint32_t)k * 8192u);
             } else {
-                s2d_dma16(wrs, (uint32_t)lane * 16u, it.wofs + (uint32_t)(q - NPA) * tapstride, lbase + (uint32_t)k * 8192u);
+                lds_dma16(wrs, (uint32_t)lane * 16u, it.wofs + (uint32_t)(q - NPA) * tapstride, lbase + (uint32_t)k * 8192u);
             }
         }
     };

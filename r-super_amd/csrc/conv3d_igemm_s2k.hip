@@ -38,14 +38,7 @@ template <int NCF> struct Geo {
     static constexpr int NV = (HROWS * 2 + NT - 1) / NT;   // 16-byte staging vectors per thread and item
 };
 
-__device__ __forceinline__ void row_to_hw_nt(int i, int& hs, int& w) {     // row_to_hw (common.hpp) without branches (conv3d_igemm_kd.hip)
-    hs = (int)((0xF00F0FF0u >> i) & 1u);
-    const unsigned long long t = i < 16 ? 0x7654765432103210ull : 0xFEDCFEDCBA98BA98ull;
-    w = (int)((t >> ((i & 15) * 4)) & 15ull);
-}
-
 struct Item { int c, td; uint32_t wofs; };
-struct Tile { uint32_t base, bad0, bad1, org; };
 
 // p.D/H/W = the half-resolution grid, FD/FH/FW the full-resolution one.  One normalised source (p.a), no residual.
 template <int NCF>

@@ -24,8 +24,6 @@
 //     the MFMAs (issue-early / write-late through registers, norm + ReLU applied while staging, double-buffered halo).
 #include "common.hpp"
 #include "kernels.hpp"
-#include <stdlib.h>
-#include <stdio.h>
 
 namespace {
 
@@ -38,9 +36,6 @@ constexpr int NVEC = 6;                         // staging vectors per thread: r
 constexpr int XB = 8 * 16 * 64 * 4;             // exchange scratch: [wave][reg][lane] f32
 constexpr int KC = 32, KP = 8;
 constexpr int NT_THREADS = 512;
-#ifndef PRIO_PERIOD
-#define PRIO_PERIOD 6
-#endif
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
@@ -56,16 +51,11 @@ __device__ __forceinline__ void swap32(float& lo, float& hi) {   // lo.lanes[32.
     lo = __uint_as_float(r[0]); hi = __uint_as_float(r[1]);
 }
 
-#ifdef RS_WS_ABLATE
-__device__ unsigned long long g_ws_prof[8 * 8];                     // block 0: [wave][loop, sync, epilogue, items, ...] shader cycles
-#endif
-
 constexpr int s_order(int i) { return i == 0 ? 0 : i == 1 ? 3 : i == 2 ? 1 : 2; }   // alternates the two accumulators
 
 // EPI: 0 forward, 1 data gradient (ReLU mask + IN-backward sums), 2 forward + residual
 // MULTI: more than one K chunk (weights re-streamed per item); NORM: sources carry (mean, rstd) -> fused IN + ReLU prologue
-// ABL (measurement builds only, RS_WS_ABLATE): 2 = no staging work, 4 = no MFMAs, 8 = no fragment reads
-template <int EPI, bool MULTI, bool NORM, int ABL = 0>
+template <int EPI, bool MULTI, bool NORM>
 __global__ __launch_bounds__(NT_THREADS, 1) void igemm_ws_kernel(IgemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* bufs = smem;                                                // 2 x HB
@@ -237,10 +227,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void igemm_ws_kernel(IgemmParams p) 
         const int kw = f / 12, r2 = f % 12, dr = r2 / 4, s = s_order(r2 % 4);
         return ((dr * HH + s) * HW + kw) * PITCH;
     };
-#ifndef RS_WS_ADIST
-#define RS_WS_ADIST 2
-#endif
-    constexpr int ADIST = RS_WS_ADIST, AR = ADIST + 1;
+    constexpr int ADIST = 2, AR = ADIST + 1;                          // fragment prefetch distance / ring
     uint4 aq[AR];
 
     f32x16_t acc[2];
@@ -282,13 +269,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void igemm_ws_kernel(IgemmParams p) 
     __syncthreads();
 
     int k_cur = 0, ch_cur = 0;                                        // (tile, chunk) of item `it`
-#ifdef RS_WS_ABLATE
-    unsigned long long pf_loop = 0, pf_sync = 0, pf_epi = 0;
-#endif
     for (int it = 0; it < nitems; ++it) {
-#ifdef RS_WS_ABLATE
-        const unsigned long long pt0 = __builtin_readcyclecounter();
-#endif
         const char* cur = bufs + (it & 1) * HB;
         char* nxt = bufs + ((it + 1) & 1) * HB;
         // (tile, chunk) of items it + 1 and it + 2
@@ -334,43 +315,35 @@ __global__ __launch_bounds__(NT_THREADS, 1) void igemm_ws_kernel(IgemmParams p) 
         // ---------------------------------------------------------------- MFMA stream with the staging in its shadow
         const int a_base = a_base0;
 #pragma unroll
-        for (int f = 0; f < ADIST; ++f) aq[f] = (ABL & 8) ? make_uint4(tid, 1, 2, 3) : *(const uint4*)(cur + a_base + frag_off(f));
+        for (int f = 0; f < ADIST; ++f) aq[f] = *(const uint4*)(cur + a_base + frag_off(f));
         constexpr int C0 = 1, CX = C0 + 4 * (NVEC - 1) + 1;
         static_assert(CX + 1 < NFRAG, "staging must fit into one item");
 #pragma unroll
         for (int f = 0; f < NFRAG; ++f) {
             const int kw = f / 12, r2 = f % 12, dr = r2 / 4, s = s_order(r2 % 4);
-            if (f + ADIST < NFRAG && !(ABL & 8)) aq[(f + ADIST) % AR] = *(const uint4*)(cur + a_base + frag_off(f + ADIST));
-            // the two waves of a SIMD take turns at the issue arbiter (otherwise the older one runs ahead and the block waits
-            // for the younger one at the barrier)
-#ifndef WS_PRIO_MODE
-#define WS_PRIO_MODE 1
-#endif
-            if (WS_PRIO_MODE == 0) { if (f % PRIO_PERIOD == 0) { if (((f / PRIO_PERIOD) & 1) ^ kh_) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); } }
-            else {                                   // progress-based (conv3d_igemm_kd.hip): the wave that is behind in the item outranks its partner
-                if (f == 0) __builtin_amdgcn_s_setprio(3);
-                if (f == NFRAG / 4) __builtin_amdgcn_s_setprio(2);
-                if (f == NFRAG / 2) __builtin_amdgcn_s_setprio(1);
-                if (f == (3 * NFRAG) / 4) __builtin_amdgcn_s_setprio(0);
-            }
+            if (f + ADIST < NFRAG) aq[(f + ADIST) % AR] = *(const uint4*)(cur + a_base + frag_off(f + ADIST));
+            // the two waves of a SIMD share the issue arbiter (by age alone the older one runs ahead and the block waits for the younger one at the
+            // barrier): progress-based priority (conv3d_igemm_kd.hip), the wave that is behind in the item outranks its partner
+            if (f == 0) __builtin_amdgcn_s_setprio(3);
+            if (f == NFRAG / 4) __builtin_amdgcn_s_setprio(2);
+            if (f == NFRAG / 2) __builtin_amdgcn_s_setprio(1);
+            if (f == (3 * NFRAG) / 4) __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int pp = 0; pp < 2; ++pp) {
                 const int kh = s - pp;
                 if (kh < 0 || kh > 2) continue;
-                if (!(ABL & 4)) mma_wa(acc[pp], wf[(dr * 3 + kh) * 3 + kw], aq[f % AR]);
+                mma_wa(acc[pp], wf[(dr * 3 + kh) * 3 + kw], aq[f % AR]);
             }
-            if (!(ABL & 2)) {
-                // f = 0: tile / chunk context of item it + 2; then per vector i: four dword slices (the 16-byte LDS write with
-                // the 4th) and, one fragment later, the global load of the same vector for item it + 2 into the freed registers
-                if (f == 0) c2 = make_ctx(k2, ch2, it + 2 < nitems);
-                if (f >= C0 && f < C0 + 4 * (NVEC - 1)) {
-                    norm_dword((f - C0) / 4, (f - C0) % 4, vm_commit);
-                    if ((f - C0) % 4 == 3) store_vec(nxt, (f - C0) / 4);
-                }
-                if (f >= C0 + 4 && f <= C0 + 4 * (NVEC - 1) && (f - C0) % 4 == 0) issue_vec(c2, (f - C0) / 4 - 1, vm_issue);
-                if (f == CX && w0_stage) { commit_vec(nxt, NVEC - 1, vm_commit); issue_vec(c2, NVEC - 1, vm_issue); }
+            // f = 0: tile / chunk context of item it + 2; then per vector i: four dword slices (the 16-byte LDS write with
+            // the 4th) and, one fragment later, the global load of the same vector for item it + 2 into the freed registers
+            if (f == 0) c2 = make_ctx(k2, ch2, it + 2 < nitems);
+            if (f >= C0 && f < C0 + 4 * (NVEC - 1)) {
+                norm_dword((f - C0) / 4, (f - C0) % 4, vm_commit);
+                if ((f - C0) % 4 == 3) store_vec(nxt, (f - C0) / 4);
             }
+            if (f >= C0 + 4 && f <= C0 + 4 * (NVEC - 1) && (f - C0) % 4 == 0) issue_vec(c2, (f - C0) / 4 - 1, vm_issue);
+            if (f == CX && w0_stage) { commit_vec(nxt, NVEC - 1, vm_commit); issue_vec(c2, NVEC - 1, vm_issue); }
             if (EPI != 0 && f == CX + 1 && last_chunk) load_ev();
             if (MULTI && (f + 1) % 12 == 0) {                         // kw group done: its 9 taps are free for the next chunk
 #pragma unroll
@@ -379,10 +352,6 @@ __global__ __launch_bounds__(NT_THREADS, 1) void igemm_ws_kernel(IgemmParams p) 
             __builtin_amdgcn_sched_barrier(0);
         }
         vmask = vm_issue;
-#ifdef RS_WS_ABLATE
-        const unsigned long long pt1 = __builtin_readcyclecounter();
-        pf_loop += pt1 - pt0;
-#endif
 
         if (last_chunk) {
             // ------------------------------------------------------------ epilogue from the accumulators
@@ -400,10 +369,6 @@ __global__ __launch_bounds__(NT_THREADS, 1) void igemm_ws_kernel(IgemmParams p) 
 #pragma unroll
                 for (int q = 0; q < 8; ++q) xw[(pp * 8 + q) * 64] = a[pp][8 + q];
             __syncthreads();                                          // exchange visible; item it fully read, item it + 1 fully written
-#ifdef RS_WS_ABLATE
-            const unsigned long long pt2 = __builtin_readcyclecounter();
-            pf_sync += pt2 - pt1;
-#endif
 #pragma unroll
             for (int pp = 0; pp < 2; ++pp) {
                 float v[KP];
@@ -447,22 +412,11 @@ __global__ __launch_bounds__(NT_THREADS, 1) void igemm_ws_kernel(IgemmParams p) 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[pp][r] = 0.f;
             }
-#ifdef RS_WS_ABLATE
-            pf_epi += __builtin_readcyclecounter() - pt2;
-#endif
         } else {
             __syncthreads();                                          // item it fully read, item it + 1 fully written
-#ifdef RS_WS_ABLATE
-            pf_sync += __builtin_readcyclecounter() - pt1;
-#endif
         }
         k_cur = k1; ch_cur = ch1;
     }
-#ifdef RS_WS_ABLATE
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0) {
-        g_ws_prof[wave * 8 + 0] = pf_loop; g_ws_prof[wave * 8 + 1] = pf_sync; g_ws_prof[wave * 8 + 2] = pf_epi; g_ws_prof[wave * 8 + 3] = (unsigned long long)nitems;
-    }
-#endif
 
     // ------------------------------------------------------------------ statistics: one partial row per (block, depth slice)
     if (p.part) {
@@ -497,34 +451,16 @@ int launch_ws(const IgemmParams& p, int epi, hipStream_t st) {
     const size_t smem = 2 * (size_t)HB + XB + (size_t)(NORM ? (p.a.C + p.b.C) : 0) * 8 + 64 * 4 + (size_t)((tiles + gx - 1) / gx) * 16;
     if (smem > 160 * 1024) return RS_ERR_UNSUPPORTED;
     dim3 grid(gx, gy, p.N), block(NT_THREADS);
-#define RS_WS_LAUNCH(E, A)                                                                                   \
+#define RS_WS_LAUNCH(E)                                                                                      \
     {                                                                                                        \
-        auto k = igemm_ws_kernel<E, MULTI, NORM, A>;                                                         \
+        auto k = igemm_ws_kernel<E, MULTI, NORM>;                                                            \
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);    \
         hipLaunchKernelGGL(k, grid, block, smem, st, p);                                                     \
         return rs_check_launch();                                                                            \
     }
-#ifdef RS_WS_ABLATE
-    struct ProfDump {                                                 // RSUPER_WS_PROF=1: print block 0's phase cycles after every launch (synchronises)
-        static void run() {
-            unsigned long long h[64];
-            (void)hipDeviceSynchronize();
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ws_prof), sizeof(h));
-            for (int w = 0; w < 8; ++w) fprintf(stderr, "ws_prof wave %d: items %llu loop %llu sync %llu epi %llu (cycles per item: %.0f %.0f %.0f)\n", w, h[w * 8 + 3], h[w * 8], h[w * 8 + 1],
-                                                h[w * 8 + 2], (double)h[w * 8] / h[w * 8 + 3], (double)h[w * 8 + 1] / h[w * 8 + 3], (double)h[w * 8 + 2] / h[w * 8 + 3]);
-        }
-    };
-    static const int prof = getenv("RSUPER_WS_PROF") ? atoi(getenv("RSUPER_WS_PROF")) : 0;
-    struct ProfGuard { int on; ~ProfGuard() { if (on) ProfDump::run(); } } guard{prof};
-    static const int abl = getenv("RSUPER_WS_ABL") ? atoi(getenv("RSUPER_WS_ABL")) : 0;
-    if (abl && ((!MULTI && NORM && epi == 0 && !p.res) || (MULTI && !NORM && epi == 1))) {
-        if (!MULTI) { if (abl == 2) RS_WS_LAUNCH(0, 2) if (abl == 4) RS_WS_LAUNCH(0, 4) if (abl == 8) RS_WS_LAUNCH(0, 8) if (abl == 12) RS_WS_LAUNCH(0, 12) if (abl == 14) RS_WS_LAUNCH(0, 14) }
-        else { if (abl == 2) RS_WS_LAUNCH(1, 2) if (abl == 4) RS_WS_LAUNCH(1, 4) if (abl == 8) RS_WS_LAUNCH(1, 8) if (abl == 12) RS_WS_LAUNCH(1, 12) if (abl == 14) RS_WS_LAUNCH(1, 14) }
-    }
-#endif
-    if (epi == 0 && p.res) RS_WS_LAUNCH(2, 0)
-    if (epi == 0) RS_WS_LAUNCH(0, 0)
-    RS_WS_LAUNCH(1, 0)
+    if (epi == 0 && p.res) RS_WS_LAUNCH(2)
+    if (epi == 0) RS_WS_LAUNCH(0)
+    RS_WS_LAUNCH(1)
 #undef RS_WS_LAUNCH
 }
 

@@ -15,25 +15,15 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "wgrad_frag.hpp"
-#include <stdio.h>
-#include <stdlib.h>
 
 namespace {
 
 constexpr int TD = 4, TH = 4, TW = 16;
-#ifndef WG_BD_
-#define WG_BD_ 3
-#endif
-constexpr int WG_BD = WG_BD_;                                         // B-fragment prefetch distance (MFMA units), classic kernel (>= 2 waves / SIMD)
-#ifndef WG_LS
-#define WG_LS 2                                                  // MFMA units between two staging loads of the next tile: 2 (round 3) -- with 5 the last loads
-#endif                                                           // were issued late in the phase and their latency was exposed behind it (same box: up3.0 301 -> 271-288 us,
+constexpr int WG_BD = 3;                                         // B-fragment prefetch distance (MFMA units), classic kernel (>= 2 waves / SIMD)
+constexpr int WG_LS = 2;                                         // MFMA units between two staging loads of the next tile: 2 (round 3) -- with 5 the last loads
+                                                                 // were issued late in the phase and their latency was exposed behind it (same box: up3.0 301 -> 271-288 us,
                                                                  // 128 -> 128 @24^3 56 -> 52-53, 64 -> 64 @48^3 76 -> 73; 1 measures the same as 2)
 constexpr int HH = TH + 2, HW = TW + 2;
-
-#ifdef RS_WG_PROF
-__device__ unsigned long long g_wg_prof[16 * 8];                 // block 0: [wave][wait+commit, barrier, issue, mfma, tiles]
-#endif
 
 template <typename T> struct WG;
 // bf16 rows are only read with ds_read_b64_tr_b16 ([4 rows] x [32 B] per 16-lane group, two groups side by side): the
@@ -164,7 +154,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 2 && MT == 2) ? 2 : 1) void 
     };
     // Staging loads of one tile, one 16-byte vector per call so that the MFMA loop can interleave them (a burst of all
     // NXV + NYV loads stalls at the CU's ~10 B/clk request rate for ~7.7k cycles per tile -- longer than the MFMA phase --
-    // with the matrix pipes idle; tools: RS_WG_PROF).  `IssueTile` holds the wave-uniform part.
+    // with the matrix pipes idle).  `IssueTile` holds the wave-uniform part.
     // Bounds are bit tests (no branches -- a branch per load makes the compiler wait for every load at once): xpm / ypm are the
     // per-thread one-hot positions of a vector's row inside the halo / tile, the tile contributes the mask of INVALID positions.
     struct IssueTile { int base, ybase; uint32_t xbad, ybad; };
@@ -220,18 +210,9 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 2 && MT == 2) ? 2 : 1) void 
     // XCD-aware tile order (wg_block_map): the splits on one XCD own a contiguous range of tiles and sweep it together
     const int tile0 = bm.tile0, tile_end = bm.tile_end, tstride = bm.tstride;
     if (tile0 < tile_end) issue(tile0);
-#ifdef RS_WG_PROF
-    unsigned long long pf[5] = {0, 0, 0, 0, 0};
-#endif
     for (int tile = tile0; tile < tile_end; tile += tstride) {
         const int n = tile / (tiles_w * tiles_h * tiles_d);
-#ifdef RS_WG_PROF
-        const unsigned long long q0 = __builtin_readcyclecounter();
-#endif
         __syncthreads();                                         // previous tile consumed
-#ifdef RS_WG_PROF
-        const unsigned long long q1 = __builtin_readcyclecounter();
-#endif
         if (norm && n != cur_n) {                                // per-sample statistics of this thread's KP channels
             cur_n = n;
 #pragma unroll
@@ -242,20 +223,10 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 2 && MT == 2) ? 2 : 1) void 
             }
         }
         commit();
-#ifdef RS_WG_PROF
-        const unsigned long long q2 = __builtin_readcyclecounter();
-#endif
         __syncthreads();
-#ifdef RS_WG_PROF
-        const unsigned long long q3 = __builtin_readcyclecounter();
-#endif
         const bool has_next = tile + tstride < tile_end;
         if (sizeof(T) != 2 && has_next) issue(tile + tstride);   // f32 parity mode: burst; bf16: interleaved with the MFMAs below
         const IssueTile nt = prepare(has_next ? tile + tstride : tile);    // last tile: harmless re-load of itself
-#ifdef RS_WG_PROF
-        const unsigned long long q4 = __builtin_readcyclecounter();
-        pf[0] += q1 - q0; pf[1] += q2 - q1; pf[2] += q3 - q2; pf[3] += q4 - q3; pf[4] += 1;
-#endif
         // ---- MFMA over the 16 (d,h) rows of the tile; k = 16 voxels along w.  Software pipelined with static
         //      indices: the operand fragments of unit (row, tap i)+1 are fetched from LDS while unit (row, i) issues.
         if constexpr (sizeof(T) == 2) {
@@ -273,9 +244,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 2 && MT == 2) ? 2 : 1) void 
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
                 const int row = u / TPW, i = u % TPW;
-#ifndef WG_PRIO
-#define WG_PRIO 0
-#endif
+                constexpr int WG_PRIO = 0;
                 if (WG_PRIO == 1) {                              // progress-based priority (conv3d_igemm_kd.hip): the wave that is behind in the tile outranks its partner
                     if (u == 0) __builtin_amdgcn_s_setprio(3);
                     if (u == NU / 4) __builtin_amdgcn_s_setprio(2);
@@ -308,18 +277,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 2 && MT == 2) ? 2 : 1) void 
                 }
             }
         }
-#ifdef RS_WG_PROF
-        pf[3] += 0; g_wg_prof[127] = 0;
-        { const unsigned long long q5 = __builtin_readcyclecounter(); if (lane == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) g_wg_prof[wave * 8 + 6] += q5 - q4; }
-#endif
     }
-#ifdef RS_WG_PROF
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0) {
-        for (int i = 0; i < 5; ++i) g_wg_prof[wave * 8 + i] = pf[i];
-        g_wg_prof[wave * 8 + 7] = g_wg_prof[wave * 8 + 6]; g_wg_prof[wave * 8 + 6] = 0;
-        g_wg_prof[wave * 8 + 5] = __builtin_readcyclecounter();
-    }
-#endif
     // ---- write this split's partial dW slab: ws[split][tap][m][cin]  (coalesced along cin)
     const int ci = c0 + (lane & 31);
     float* slab = p.ws + (size_t)bm.bz * 27 * Mtot * cin_total;
@@ -567,20 +525,7 @@ int launch(const WgradParams& p, hipStream_t st, bool reduce) {
     dim3 grid(nch, mgroups * (NTAPS == 27 ? 1 : 3), p.splits), block(64 * NW);
     auto k = wgrad_kernel<T, MT, NTAPS, TR, NW>;
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#ifdef RS_WG_PROF
-    static unsigned long long t_prev = 0;
-#endif
     hipLaunchKernelGGL(k, grid, block, smem, st, p);
-#ifdef RS_WG_PROF
-    if (getenv("RSUPER_WG_PROF")) {
-        unsigned long long h[128];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wg_prof), sizeof(h));
-        for (int w = 0; w < NW; w += 3) fprintf(stderr, "wg_prof MT%d taps%d NW%d wave %d: tiles %llu | per tile: barrier1 %.0f commit(+wait loads) %.0f barrier2 %.0f issue %.0f mfma %.0f\n", MT, NTAPS, NW, w, h[w * 8 + 4],
-                                             (double)h[w * 8] / h[w * 8 + 4], (double)h[w * 8 + 1] / h[w * 8 + 4], (double)h[w * 8 + 2] / h[w * 8 + 4], (double)h[w * 8 + 3] / h[w * 8 + 4], (double)h[w * 8 + 7] / h[w * 8 + 4]);
-        (void)t_prev;
-    }
-#endif
     if (reduce) launch_reduce(p, st);
     return rs_check_launch();
 }

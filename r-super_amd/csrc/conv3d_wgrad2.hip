@@ -7,7 +7,7 @@
 // Same contraction, tiling (4x4x16 voxels x 32 input channels per block), fragment reads (ds_read_b64_tr_b16 on 64-byte rows), slab format and
 // reduction as conv3d_wgrad.hip; x_hat = relu((x - mean) * rstd) is recomputed from x while a tile is staged (never stored).
 //
-// What conv3d_wgrad.hip loses per 256-voxel tile (RS_WG_PROF cycle stamps, 64-row x 27-tap blocks): the two waves of a SIMD need 6.0 k / 9.2 k cycles
+// What conv3d_wgrad.hip loses per 256-voxel tile (cycle stamps, 64-row x 27-tap blocks): the two waves of a SIMD need 6.0 k / 9.2 k cycles
 // for an MFMA phase whose matrix-pipe time is 7.2 k, then the pipes stand still for ~2.6 k cycles of commit (InstanceNorm + ReLU on the staged
 // vectors, ds_write_b128) and ~1 k of barrier skew: ~12 k cycles per 6.9 k of MFMA.  Counters: 2.3 LDS instructions per MFMA, LDS pipe 57 % busy.
 //   (1) Operand re-use.  A fragment x_hat[(d', h'), kw .. kw+15] is the B operand of EVERY tap (kd, kh, kw) whose output row (d' - kd, h' - kh) lies
@@ -23,15 +23,9 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "wgrad_frag.hpp"
-#include <stdio.h>
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-#ifdef WG2_PROF
-__device__ unsigned long long g_wg2_prof[8 * 4];                 // block 0: [wave][loop cycles, barrier cycles, tiles, -]
-#endif
 
 constexpr int TD = 4, TH = 4, TW = 16, HD = TD + 2, HH = TH + 2, HW = TW + 2;
 constexpr int XROWS = HD * HH * HW;                              // 648 halo rows of 64 B (32 channels)
@@ -42,6 +36,7 @@ constexpr int NT = 512, NW = 8;
 // dY needs no arithmetic on its way into LDS: `buffer_load_dwordx4 ... lds` copies 1 KB per wave instruction from per-lane global offsets into a
 // lane-linear LDS image (lane l -> M0 + 16 l), out-of-range offsets arrive as zeros; semantics pinned by tools/ubench/lds_dma_probe.hip.  The
 // compiler does not see the instruction: completion is waited for by an explicit counted vmcnt before the tile barrier.
+// (lds_dma16 of common.hpp takes a scalar offset register where this form encodes the constant 0: another instruction, so this one stays.)
 __device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t& rs, uint32_t voff, uint32_t lds_byte) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" : : "v"(voff), "s"(lds_byte), "s"(rs) : "memory", "m0");
 }
@@ -220,18 +215,11 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgradParams p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 c = ncst[j];
-#ifndef WG2_PKFMA
                     // two v_fma_f32, not one v_pk_fma_f32: beside MFMAs the packed f32 forms cost ~22 cycles more per instruction (MI355X_MICROARCH.md, filler prices)
                     float x0, x1;
                     asm("v_fma_f32 %0, %1, %2, %3" : "=v"(x0) : "v"(__uint_as_float(w[j] << 16)), "v"(c.x), "v"(c.z));
                     asm("v_fma_f32 %0, %1, %2, %3" : "=v"(x1) : "v"(__uint_as_float(w[j] & 0xffff0000u)), "v"(c.y), "v"(c.w));
                     i16x2_t v = __builtin_bit_cast(i16x2_t, f2bf2(x0, x1));
-#else
-                    f32x2_t x = {__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xffff0000u)};
-                    const f32x2_t s2 = {c.x, c.y}, b2 = {c.z, c.w};
-                    x = __builtin_elementwise_fma(x, s2, b2);
-                    i16x2_t v = __builtin_bit_cast(i16x2_t, f2bf2(x[0], x[1]));
-#endif
                     const i16x2_t z = {0, 0};
                     v = __builtin_elementwise_max(v, z);
                     o[j] = __builtin_bit_cast(uint32_t, v) & m;
@@ -251,12 +239,8 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgradParams p) {
         // younger one gets what is left (cycle stamps, 32 -> 32 @96^3, staging off: older wave 2.0 k cycles for its 56 MFMAs, then 1.8 k at the barrier;
         // younger 3.7 k).  So the two programs are made complementary instead of identical: the older wave multiplies first and stages in the second
         // half of its steps, the younger one stages in the first half (while the matrix pipe belongs to its partner) and multiplies after.
-#ifndef WG2_HOOK_MODE
-#define WG2_HOOK_MODE 1
-#endif
-        constexpr int HMODE = WG2_HOOK_MODE;                     // 0: hooks spread evenly; 1: complementary halves; 2: the other way round
-        constexpr bool late = HMODE == 0 ? false : ((G < 2) == (HMODE == 1));
-        auto hook_step = [&](int i) constexpr { return HMODE == 0 ? (i * S.n) / NV : (late ? S.n / 2 : 0) + (i * (S.n / 2)) / NV; };
+        constexpr bool late = G < 2;
+        auto hook_step = [&](int i) constexpr { return (late ? S.n / 2 : 0) + (i * (S.n / 2)) / NV; };
         f32x16_t acc[7];
 #pragma unroll
         for (int i = 0; i < 7; ++i)
@@ -281,22 +265,14 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgradParams p) {
         asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NV) : "memory");      // the dY pieces of tile 0 (the x loads of tile 1 stay in flight)
         __syncthreads();
 
-#ifdef WG2_PROF
-        unsigned long long pf_loop = 0, pf_bar = 0;
-#endif
         int it = 0;
         for (int tile = tile0; tile < tile_end; tile += tstride, ++it) {
-#ifdef WG2_PROF
-            const unsigned long long q0 = __builtin_readcyclecounter();
-#endif
             const char* buf = smem + (it & 1) * BUF;
             char* nxt = smem + ((it + 1) & 1) * BUF;
             const IssueTile t2 = fetch_desc(it + 2);             // t1: the tile committed during this one; t2: the tile whose loads are issued during it
             load_norm(t1.n);
-#ifndef WG2_SKIP_STAGE
 #pragma unroll
             for (int k = 0; k < YK; ++k) dma_y(t1, k, (uint32_t)((it + 1) & 1) * BUF);      // first VMEM operations of the tile: NV x loads follow
-#endif
             auto fetch_a = [&](int row) { return frag_bf16<1>(buf + ya_off + (row * TW) * 64, 64); };
             auto fetch_b = [&](int s) { return frag_bf16<1>(buf + x_off + ((S.dp[s] * HH + S.hp[s]) * HW + S.kw[s]) * 64, 64); };
             constexpr int BR = BD + 1;
@@ -307,9 +283,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgradParams p) {
             for (int s = 0; s < BD; ++s) bq[s] = fetch_b(s);
 #pragma unroll
             for (int s = 0; s < S.n; ++s) {
-#ifndef WG2_PRIO
-#define WG2_PRIO 1
-#endif
+                constexpr int WG2_PRIO = 1;
                 // progress-based priority (conv3d_igemm_kd.hip): the wave of a SIMD that is behind in the tile outranks its partner
                 if (WG2_PRIO == 1) {
                     if (s == 0) __builtin_amdgcn_s_setprio(3);
@@ -337,37 +311,19 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgradParams p) {
                     if (!pair_in_group(G, pidx) || !unit_valid(NDL, S.dp[s], S.hp[s], pidx)) continue;
                     const int d = S.dp[s] - pidx / 3, h = S.hp[s] - pidx % 3;
                     const int slot = G < 3 ? pidx : (pidx - 7) * 3 + S.kw[s];
-#ifndef WG2_SKIP_MMA                                             // ablation switches (tools/wg2_ablate.sh)
                     mma32<bf16_t>(acc[slot], a[(d % AP) * TH + h], bq[s % BR]);
-#else
-                    if (s == 0) mma32<bf16_t>(acc[slot], a[(d % AP) * TH + h], bq[s % BR]);
-#endif
                 }
-#ifndef WG2_SKIP_STAGE
                 // staging hooks: vector i of tile t + 1 is normalised + written into the other buffer, then its register takes the load of tile t + 2
 #pragma unroll
                 for (int i = 0; i < NV; ++i)
                     if (s == hook_step(i)) { commit_v(nxt, i, t1); issue_v(t2, i); }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
-#ifdef WG2_PROF
-            const unsigned long long q1 = __builtin_readcyclecounter();
-#endif
-#ifndef WG2_SKIP_STAGE
             asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NV) : "memory");  // this tile's dY pieces have landed; the NV x loads issued after them stay in flight
-#endif
-            __syncthreads();
-#ifdef WG2_PROF
-            const unsigned long long q2 = __builtin_readcyclecounter();
-            pf_loop += q1 - q0; pf_bar += q2 - q1;
-#endif                                     // tile t consumed, tile t + 1 complete in the other buffer
+            __syncthreads();                                             // tile t consumed, tile t + 1 complete in the other buffer
             t1 = t2;
         }
 
-#ifdef WG2_PROF
-        if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0) { g_wg2_prof[wave * 4] = pf_loop; g_wg2_prof[wave * 4 + 1] = pf_bar; g_wg2_prof[wave * 4 + 2] = (unsigned long long)it; }
-#endif
         // ---- 32-row blocks: the two depth halves meet in LDS (the tile buffers are free now); wave wsel = 0 of each pair holds the sum
         if constexpr (MT == 1) {
             float* red = (float*)smem + (size_t)g * 7 * 16 * 64 + lane;
@@ -422,16 +378,6 @@ int launch2(const WgradParams& p, hipStream_t st) {
     auto k = wgrad2_kernel<MT, BD, NORM>;
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     hipLaunchKernelGGL(k, grid, block, smem, st, p);
-#ifdef WG2_PROF
-    if (getenv("RSUPER_WG2_PROF")) {
-        unsigned long long h[32];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wg2_prof), sizeof(h));
-        fprintf(stderr, "wg2_prof MT%d norm%d:", MT, (int)NORM);
-        for (int w = 0; w < 8; ++w) fprintf(stderr, " w%d(g%d) loop %.0f bar %.0f |", w, w >> 1, (double)h[w * 4] / h[w * 4 + 2], (double)h[w * 4 + 1] / h[w * 4 + 2]);
-        fprintf(stderr, " tiles %llu\n", h[2]);
-    }
-#endif
     return RS_OK;
 }
 
@@ -439,9 +385,7 @@ int launch2(const WgradParams& p, hipStream_t st) {
 
 // what the kernel requires of a launch is wgrad2_supported (wgrad_plan.hpp); mt: 32-row groups of dY per block, from the plan
 int rs_launch_wgrad2(const WgradParams& p, int mt, hipStream_t st) {
-#ifndef WG2_BD
-#define WG2_BD 2
-#endif
+    constexpr int WG2_BD = 2;                                    // B-fragment prefetch distance (MFMA steps)
     if (p.xa.mr) return mt == 1 ? launch2<1, WG2_BD, true>(p, st) : launch2<2, WG2_BD, true>(p, st);
     return mt == 1 ? launch2<1, WG2_BD, false>(p, st) : launch2<2, WG2_BD, false>(p, st);
 }

@@ -19,14 +19,8 @@ namespace {
 
 constexpr int TW2 = 16, HW2 = 2 * TW2 + 1;                       // dY tile width, halo width (33 = 17 even + 16 odd positions)
 
-#ifndef S2W_NW
-#define S2W_NW 8
-#endif
-#ifndef S2W_SKIP
-#define S2W_SKIP 0                                               // profiling switches (wrong results): 1 no MFMA phase, 2 no norm + ReLU, 4 no LDS commit, 8 no global loads of x, 16 no slab write, 32 no tiles
-#endif
 template <typename T> struct S2W;
-template <> struct S2W<bf16_t> { static constexpr int XP = 64, MT = 2, NW = S2W_NW, TD2 = 2, TH2 = 4, YP = 192; };   // LDS 95.0 + 24.6 KB
+template <> struct S2W<bf16_t> { static constexpr int XP = 64, MT = 2, NW = 8, TD2 = 2, TH2 = 4, YP = 192; };   // LDS 95.0 + 24.6 KB
 template <> struct S2W<float> { static constexpr int XP = 144, MT = 1, NW = 4, TD2 = 1, TH2 = 4, YP = 144; };   // LDS 128.3 + 9.2 KB
 
 // first LDS row (within one (d, h) line of the halo) of the 16 voxels 2q + kw: kw = 0 -> even 0.., 1 -> odd 0.., 2 -> even 1..
@@ -54,7 +48,7 @@ __global__ __launch_bounds__(64 * S2W<T>::NW, 1) void wgrad_s2_kernel(WgradParam
     const int m0 = blockIdx.y * MT * 32;
     const bool norm = xs.mr != nullptr;
     const int tiles_w = (OW + TW2 - 1) / TW2, tiles_h = (OH + TH2 - 1) / TH2, tiles_d = (OD + TD2 - 1) / TD2;
-    const int tiles = (S2W_SKIP & 32) ? 0 : tiles_w * tiles_h * tiles_d * p.N;
+    const int tiles = tiles_w * tiles_h * tiles_d * p.N;
 
     f32x16_t acc[TPW];
 #pragma unroll
@@ -118,10 +112,8 @@ __global__ __launch_bounds__(64 * S2W<T>::NW, 1) void wgrad_s2_kernel(WgradParam
             const int d = dlo + (xpos[i] & 7), h = hlo + ((xpos[i] >> 3) & 15), w = wlo + ((xpos[i] >> 7) & 63);
             const bool ok = xpos[i] >= 0 && x_cok && (unsigned)d < (unsigned)p.D && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
             const uint32_t off = ok ? (uint32_t)(((n * p.D + d) * p.H + h) * p.W + w) * xrowb + xcol : 0xFFFFFFFFu;   // out of range -> zeros
-            if (!(S2W_SKIP & 8)) {
-                const auto q = __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, 0);
-                px[i] = make_uint4(q[0], q[1], q[2], q[3]);
-            } else px[i] = make_uint4(off, off, off, off);
+            const auto q = __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, 0);
+            px[i] = make_uint4(q[0], q[1], q[2], q[3]);
             xmask = (xmask & ~(1u << i)) | (ok ? (1u << i) : 0u);
             __builtin_amdgcn_sched_barrier(0);                   // one address at a time (hoisting all NXV offsets overflows the register file)
         }
@@ -139,8 +131,8 @@ __global__ __launch_bounds__(64 * S2W<T>::NW, 1) void wgrad_s2_kernel(WgradParam
 #pragma unroll
         for (int i = 0; i < NXV; ++i) {
             uint4 q = px[i];
-            if (!(S2W_SKIP & 2) && norm && ((xmask >> i) & 1u)) q = norm_relu16<T>(q, sc_, nb_);
-            if ((!(S2W_SKIP & 4) || q.x == 0x12345u) && xpos[i] >= 0) *(uint4*)(x_lds + (xpos[i] >> 13) * XP) = q;
+            if (norm && ((xmask >> i) & 1u)) q = norm_relu16<T>(q, sc_, nb_);
+            if (xpos[i] >= 0) *(uint4*)(x_lds + (xpos[i] >> 13) * XP) = q;
         }
 #pragma unroll
         for (int i = 0; i < NYV; ++i)
@@ -166,8 +158,7 @@ __global__ __launch_bounds__(64 * S2W<T>::NW, 1) void wgrad_s2_kernel(WgradParam
         commit();
         __syncthreads();
         if (tile + p.splits < tiles) issue(tile + p.splits);     // next tile's loads fly under this tile's MFMAs
-        if constexpr (S2W_SKIP & 1) {
-        } else if constexpr (sizeof(T) == 2) {
+        if constexpr (sizeof(T) == 2) {
             const char* ya_base = yt + wm * 64 + frag_lane_off<1>(YP, lane);
             const char* xl = xh + frag_lane_off<1>(XP, lane);
             auto fetch_a = [&](int row) { return frag_bf16<1>(ya_base + (row * TW2) * YP, YP); };
@@ -209,7 +200,6 @@ __global__ __launch_bounds__(64 * S2W<T>::NW, 1) void wgrad_s2_kernel(WgradParam
         }
     }
     // ---- partial dW slab of this split: ws[split][tap][m][cin]
-    if ((S2W_SKIP & 16) && acc[0][0] != 12345.f) return;
     const int ci = c0 + (lane & 31);
     float* slab = p.ws + (size_t)blockIdx.z * 27 * Mtot * xs.C;
 #pragma unroll

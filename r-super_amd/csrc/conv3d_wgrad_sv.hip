@@ -19,7 +19,6 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "wgrad_frag.hpp"
-#include <stdlib.h>
 
 namespace {
 
@@ -78,7 +77,6 @@ __global__ __launch_bounds__(NT, 2) void wgrad_sv_kernel(WgradParams p, int P, i
     __syncthreads();
 
     // ---- stage the x_hat image: vector v = (row, 16-byte slot); rows of the zero border and channels past C become zeros
-#ifndef WGSV_SKIP_STAGE
     {
         const int slot = tid & 3;
         float sc_[8], nb_[8];
@@ -143,7 +141,6 @@ __global__ __launch_bounds__(NT, 2) void wgrad_sv_kernel(WgradParams p, int P, i
             }
         }
     }
-#endif
     __syncthreads();
 
     // ---- MFMA phase: wave g owns the taps g, g + 4, ...; per k-step one A fragment (16 consecutive dY rows) and one gathered B fragment per tap
@@ -193,9 +190,6 @@ __global__ __launch_bounds__(NT, 2) void wgrad_sv_kernel(WgradParams p, int P, i
     // two k-steps per iteration on fixed register sets: the operands of step k + 1 are requested before the MFMAs of step k issue
     Ops e, o;
     load_ops(0, e);
-#ifdef WGSV_SKIP_MMA
-    if (nks > 1000000)
-#endif
     for (int ks = 0; ks < nks; ks += 2) {
         if (ks + 1 < nks) load_ops(ks + 1, o);
         __builtin_amdgcn_sched_barrier(0);
@@ -217,9 +211,6 @@ __global__ __launch_bounds__(NT, 2) void wgrad_sv_kernel(WgradParams p, int P, i
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = m0 + cd_row32(r, lane);
-#ifdef WGSV_SKIP_STORE
-            if (acc[i][r] == 12345.678f)
-#endif
             if (m < Mtot && ci < xs.C) slab[((size_t)tl * Mtot + m) * cin_total + cin_base + (lane & 31)] = acc[i][r];
         }
     }

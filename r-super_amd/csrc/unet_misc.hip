@@ -872,9 +872,6 @@ struct UpInParams {
     const void* u; int ldu;
     const float* mr; const float* gm;
 };
-#ifndef UP4_SL
-#define UP4_SL 2
-#endif
 // LAZY: every loaded vector of g gets the tail of in_bwd_finalize (with the vector of u at the same voxel) and the rounding of the tensor that launch
 // would have written; weights and accumulation order are untouched, so dx is bit for bit that of in_bwd_finalize + this kernel.  The second operand
 // buffers and the 32 per-channel constants do not fit three blocks per CU: the lazy instantiations run two.
@@ -882,7 +879,7 @@ template <int NT, bool LAZY>
 __global__ __launch_bounds__(256, LAZY ? 2 : 3) void upsample_bwd4_kernel(UpInParams p, int nbx) {
     typedef bf16_t T;
     constexpr int CPT = 8, NWD = CPT / 2;                        // channels per thread (one 16-byte vector), 32-bit words of it
-    constexpr int SL = UP4_SL;                                   // row slots: SL - 1 rows of loads in flight behind the one being reduced
+    constexpr int SL = 2;                                        // row slots: SL - 1 rows of loads in flight behind the one being reduced
     __shared__ float Wd[UP4_ROWS][2], Wh[UP4_ROWS][2];
     __shared__ float4 W4[UP4_ROWS * UP4_ROWS];                   // row (a, b) -> (wd0 wh0, wd0 wh1, wd1 wh0, wd1 wh1)
     __shared__ int span[4];                                      // od0, rd, oh0, rh
@@ -1097,9 +1094,6 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(StemParams p) {
 // exact-f32 v_mfma_f32_32x32x2_f32 chain (14 steps cover the 27 taps + one zero pad).  A = weights (row = channel, held
 // in 14 registers per lane for the whole block), B = gathered input (column = voxel).  A lane ends up with 16 channels
 // of one voxel = four 4-channel groups -> 8-byte (bf16) / 16-byte (f32) stores.  Block = 256 consecutive voxels.
-#ifndef STEM_DIRECT_STORE
-#define STEM_DIRECT_STORE 0
-#endif
 template <typename T>
 __global__ __launch_bounds__(256) void stem_fwd_mfma_kernel(StemParams p) {
     __shared__ float tile[256 * 33];
@@ -1143,7 +1137,6 @@ __global__ __launch_bounds__(256) void stem_fwd_mfma_kernel(StemParams p) {
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int s = 0; s < 14; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[s], xa[s], acc, 0, 0, 0);
-        T* o = (T*)p.y + ((size_t)n * vox + (ok ? v : 0)) * p.ldy;
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
             const int c0 = 8 * r4 + 4 * kk;                      // channels c0 .. c0+3 of voxel idx (cd_row32 layout)
@@ -1153,17 +1146,10 @@ __global__ __launch_bounds__(256) void stem_fwd_mfma_kernel(StemParams p) {
                 q[j] = Elem<T>::rnd(acc[r4 * 4 + j]);
                 tile[vl * 33 + c0 + j] = ok ? q[j] : 0.f;
             }
-            if (STEM_DIRECT_STORE && ok && c0 < C) {
-                if (sizeof(T) == 2) {
-                    *(uint2*)(o + c0) = make_uint2(f2bf2(q[0], q[1]), f2bf2(q[2], q[3]));
-                } else {
-                    *(float4*)((float*)o + c0) = make_float4(q[0], q[1], q[2], q[3]);
-                }
-            }
         }
     }
     __syncthreads();
-    if (!STEM_DIRECT_STORE) {
+    {
         // the block's 256 voxels x C channels leave through the statistics tile as 16-byte vectors, consecutive lanes -> consecutive addresses (the
         // accumulator layout gives a lane 4 channels of one voxel: 8-byte stores 64 bytes apart, a quarter of every 32-byte sector per instruction)
         constexpr int KP = Elem<T>::KP;

@@ -20,5 +20,4 @@ timeout 1500 python bench.py --full > profiles/r04_bench_default.json
 tail -c 300 profiles/r04_bench_default.json
 timeout 300 python tools/ddp_bucket_timeline.py 6 > gpurun_out/r04_ddp_bucket_timeline.txt 2>&1
 timeout 300 python tools/xhat_probe.py > gpurun_out/r04_xhat_probe.txt 2>&1
-timeout 300 bash tools/wg2_prof.sh "-DWG2_SKIP_STAGE" > /dev/null 2>&1; cp gpurun_out/wg2_prof.txt gpurun_out/r04_wg2_prof.txt
 timeout 600 bash tools/mf_kstats.sh > /dev/null 2>&1
