@@ -1417,6 +1417,207 @@ def check_wgrad_sliced_dy(N, S, Ca, Cout, seed=0):
     return result(f'wgrad_sliced_dy[bf16 N{N} S{S} {Ca}->2x{Cout}]', e, 3e-3, f'dw {e:.2e}')
 
 
+# ================================================================================================ integer operands: exact, no tolerance (tests/exact_ref.py)
+def _exact_result(name, notes, extra=''):
+    """err = number of comparisons that found a mismatch; tol 0.  notes: the non-empty strings of exact_ref.mismatch_note."""
+    bad = [n for n in notes if n]
+    return result(name, float(len(bad)), 0.0, '; '.join(([extra] if extra else []) + (bad or ['equal to float64 at every element'])))
+
+
+class _wgrad_pins:
+    """rsuper_conv3_wgrad2_min_tiles (None: leave the default) and RSUPER_WGRAD_TR for one launch, restored on exit."""
+
+    def __init__(self, thr, tr):
+        self.thr, self.tr = thr, tr
+
+    def __enter__(self):
+        from rsuper_amd.hip import ops
+        self.L = ops._L()
+        self.old_thr, self.old_tr = self.L.rsuper_conv3_wgrad2_min_tiles(-1), os.environ.get('RSUPER_WGRAD_TR')
+        if self.thr is not None:
+            self.L.rsuper_conv3_wgrad2_min_tiles(self.thr)
+        if self.tr is not None:
+            os.environ['RSUPER_WGRAD_TR'] = str(self.tr)
+        return self.L
+
+    def __exit__(self, *exc):
+        self.L.rsuper_conv3_wgrad2_min_tiles(self.old_thr)
+        if self.tr is not None:
+            if self.old_tr is None:
+                os.environ.pop('RSUPER_WGRAD_TR', None)
+            else:
+                os.environ['RSUPER_WGRAD_TR'] = self.old_tr
+
+
+WGRAD_KERNEL_NAMES = ('tile', 'wgrad2', 'sv')            # plan[0] of rsuper_conv3_wgrad_plan (lib.WGRAD_TILE, WGRAD_2, WGRAD_SV)
+
+
+def _wgrad_launch_plan(L, dt, Ca, Cb, Ya, Yb, N, S, src_flags):
+    """The plan of the launch ops.wgrad is about to make (same arguments, same RSUPER_WGRAD_TR, same threshold): (kernel name, splits, cfg, mt)."""
+    import ctypes
+    from rsuper_amd.hip import ops
+    plan = (ctypes.c_int * 4)()
+    assert L.rsuper_conv3_wgrad_plan(ops._DT[dt], ops.use_tr(), Ca, Cb, Ya, Yb, N, *S, src_flags, 0, plan) == 0
+    assert plan[1] == L.rsuper_conv3_wgrad_splits(ops._DT[dt], Ca, Cb, Ya, Yb, N, *S) and plan[1] >= 1, tuple(plan)
+    return (WGRAD_KERNEL_NAMES[plan[0]], plan[1], plan[2], plan[3])
+
+
+def _wgrad_sources(o, dt, Ya, Yb, sliced):
+    """ops.Src of a weight-gradient case's host operands (exact_ref.wgrad_operands / the real-valued dict of check_wgrad_exact)."""
+    from rsuper_amd.hip import ops
+    sa = ops.Src(to_cl(o['xa'], dt), mr=o['mra'].to(DEV) if o['mra'] is not None else None)
+    sb = ops.Src(to_cl(o['xb'], dt), mr=o['mrb'].to(DEV) if o['mrb'] is not None else None) if o['xb'] is not None else None
+    if sliced:                                                          # ld = Ya + Yb, as check_wgrad_sliced_dy builds them
+        dfull = to_cl(o['dy'], dt)
+        return sa, sb, ops.Src(dfull, C=Ya), ops.Src(dfull, C=Yb, off=Ya)
+    return sa, sb, ops.Src(to_cl(o['dy'][:, :Ya], dt)), ops.Src(to_cl(o['dy'][:, Ya:], dt)) if Yb else None
+
+
+def check_wgrad_int(kernel, cfg, mt, mode, N, S, Ca, Cb, Ya, Yb, norm, thr, tr, sliced=False, narrow=False):
+    """Stride-1 3x3x3 weight gradient on integer operands (tests/exact_ref.py): x in [-3, 3], dY in [-2, 2], integer means and power-of-two rstd per sample
+    and channel, so the prologue, the bf16 rounding and the f32 accumulation are all exact in any order and dW must EQUAL the float64 gradient at every
+    element -- one lost, doubled or misplaced voxel x channel term fails, at any reduction length.  The launch is first asserted to run what the case
+    names: rsuper_conv3_wgrad_plan with the launch's own arguments under threshold thr (rsuper_conv3_wgrad2_min_tiles; None: default) and RSUPER_WGRAD_TR=tr.
+    norm: 'raw' | 'both' | 'mixed' (a normalised, b raw: src_flags bit 0).  dW starts as NaN.  The first index of a mismatch is (row, x channel, kd, kh, kw)."""
+    import exact_ref as er
+    from rsuper_amd.hip import ops
+    dt = DT[mode]
+    o = er.wgrad_operands(N, S, Ca, Cb, Ya, Yb, norm, 1, narrow)
+    ref, mag = er.wgrad_ref(N, S, Ca, Cb, Ya, Yb, norm, 1, narrow)
+    assert er.exact_ok(mag), 'the case is not exact in f32: shrink it or narrow its ranges'
+    sa, sb, y1, y2 = _wgrad_sources(o, dt, Ya, Yb, sliced)
+    dw1 = torch.full((Ya, Ca + Cb, 3, 3, 3), float('nan'), device=DEV)
+    dw2 = torch.full((Yb, Ca + Cb, 3, 3, 3), float('nan'), device=DEV) if Yb else None
+    with _wgrad_pins(thr, tr) as L:
+        plan = _wgrad_launch_plan(L, dt, Ca, Cb, Ya, Yb, N, S, int(norm == 'mixed'))
+        assert (plan[0], plan[2], plan[3]) == (kernel, cfg, mt), f'the case names {(kernel, cfg, mt)}, the launch would run {plan}'
+        ops.wgrad(sa, sb, y1, y2, dw1, dw2, (N,) + tuple(S))
+        torch.cuda.synchronize()
+    notes = [er.mismatch_note('dW a', dw1, ref[:Ya])] + ([er.mismatch_note('dW b', dw2, ref[Ya:])] if Yb else [])
+    return _exact_result(f'wgrad_int[{mode} tr{tr} thr{thr} N{N} S{S} {Ca}+{Cb}->{Ya}+{Yb} {norm}{" sliced" if sliced else ""}]', notes,
+                         f'plan (kernel, splits, cfg, mt) {plan}')
+
+
+def check_wgrad_s2_int(mode, N, S, Ca, Ya, Yb):
+    """ops.wgrad_s2 (csrc/conv3d_wgrad_s2.hip) on the integer operands of tests/exact_ref.py: equal to the float64 gradient of
+    F.conv3d(x_hat, w, stride=2, padding=1) at every element, bf16 and f32.  dW starts as NaN."""
+    import exact_ref as er
+    from rsuper_amd.hip import ops
+    dt = DT[mode]
+    o = er.wgrad_operands(N, S, Ca, 0, Ya, Yb, 'both', 2)
+    ref, mag = er.wgrad_ref(N, S, Ca, 0, Ya, Yb, 'both', 2)
+    assert er.exact_ok(mag)
+    sa, _, y1, y2 = _wgrad_sources(o, dt, Ya, Yb, False)
+    dw1 = torch.full((Ya, Ca, 3, 3, 3), float('nan'), device=DEV)
+    dw2 = torch.full((Yb, Ca, 3, 3, 3), float('nan'), device=DEV) if Yb else None
+    ops.wgrad_s2(sa, y1, y2, dw1, dw2, (N,) + tuple(S))
+    torch.cuda.synchronize()
+    notes = [er.mismatch_note('dW a', dw1, ref[:Ya])] + ([er.mismatch_note('dW b', dw2, ref[Ya:])] if Yb else [])
+    return _exact_result(f'wgrad_s2_int[{mode} N{N} S{S} {Ca}->{Ya}+{Yb}]', notes)
+
+
+def _column_slice(t, pad=4):
+    """t (R, C) on the device as the slice [:R, pad:pad + C] of an (R + 1, C + 2 pad) matrix whose other columns and last (guard) row hold NaN."""
+    wide = torch.full((t.shape[0] + 1, t.shape[1] + 2 * pad), float('nan'), device=DEV)
+    wide[:t.shape[0], pad:pad + t.shape[1]] = t.to(DEV)
+    return wide[:t.shape[0], pad:pad + t.shape[1]]
+
+
+def check_pointwise_int(mode, R, K, N, sliced=False):
+    """Everything check_pointwise computes (forward with bias and with the residual, data gradient, weight and bias gradient of csrc/pointwise.hip) on the
+    integer operands of tests/exact_ref.py: equal to the float64 matmul at every element.  sliced: x, dy and the weight gradient's operands are column
+    slices [:, 4:4 + width] of matrices 8 columns wider (stride(0) != width, which ops.pointwise_gemm / pointwise_wgrad accept); every other column and
+    a guard row after the last hold NaN, so one element read outside the slice shows.  The first index of a mismatch is (row, column) of that result."""
+    import exact_ref as er
+    from rsuper_amd.hip import ops
+    comp = DT[mode]
+    o = er.pointwise_operands(R, K, N)
+    refs = er.pointwise_ref(o)
+    assert all(er.exact_ok(m) for _, m in refs.values())
+    put = _column_slice if sliced else (lambda t: t.to(DEV))
+    x, dy, w, b, res = put(o['x']), put(o['dy']), o['w'].to(DEV), o['b'].to(DEV), o['res'].to(DEV)
+    got = dict(y=ops.pointwise_gemm(x, w, b, 0, comp), yr=ops.pointwise_gemm(x, w, b, 0, comp, res), dx=ops.pointwise_gemm(dy, w, None, 1, comp))
+    got['dw'], got['db'] = ops.pointwise_wgrad(dy, x, True, comp)
+    torch.cuda.synchronize()
+    return _exact_result(f'pointwise_int[{mode} R{R} K{K} N{N}{" sliced" if sliced else ""}]', [er.mismatch_note(k, got[k], refs[k][0]) for k in refs])
+
+
+# ================================================================================================ real operands: the rounding, at derived bounds
+def _worst_ratio(got, ref, bound):
+    r = (got.detach().cpu().double() - ref).abs() / (bound + 1e-300)
+    r = torch.where(torch.isfinite(r), r, torch.full_like(r, float('inf')))
+    return r.max().item()
+
+
+def check_pointwise_exact(R, K, N, seed=107):
+    """bf16 csrc/pointwise.hip on N(0, 1) operands against float64 on EXACTLY the operands the kernel multiplies (x, w, dy rounded to bf16 with
+    round-to-nearest-even, as pack16<bf16_t> does; bias and residual are added unrounded in f32) -- what integers cannot see: the rounding mode.
+    Per element |got - ref| <= (L / 8 + 10) 2^-24 mag for the forward and the data gradient, L the reduction length of that GEMM (K forward, N data
+    gradient) and mag = |x||w|^T + |b| + |res|: L / 8 roundings of the f32 accumulator (one per MFMA k-step and lane half, check_conv_exact's count), the
+    three adds of the k-split, the bias, the residual and the same slack of 4.  Weight gradient: (R / 8 + S + 4) 2^-24 |dy|^T|x|, S the slabs of the plan.
+    One missing product is >= 7 bounds at R <= 4160; truncating the operands instead of rounding them > 100.  err = the worst ratio, <= 1."""
+    import ctypes
+    from rsuper_amd.hip import ops, lib as _lib
+    g = torch.Generator().manual_seed(seed)
+    x, w, b = torch.randn(R, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K), torch.randn(N, generator=g)
+    dy, res = torch.randn(R, N, generator=g), torch.randn(R, N, generator=g)
+    xb, wb, dyb = x.bfloat16().double(), w.bfloat16().double(), dy.bfloat16().double()
+    comp = torch.bfloat16
+    y = ops.pointwise_gemm(x.to(DEV), w.to(DEV), b.to(DEV), 0, comp)
+    yr = ops.pointwise_gemm(x.to(DEV), w.to(DEV), b.to(DEV), 0, comp, res.to(DEV))
+    dx = ops.pointwise_gemm(dy.to(DEV), w.to(DEV), None, 1, comp)
+    dw, _ = ops.pointwise_wgrad(dy.to(DEV), x.to(DEV), False, comp)
+    torch.cuda.synchronize()
+    plan = (ctypes.c_int * 10)()
+    _lib.check(ops._L().rsuper_mf_plan(_lib.MF_PW_WGRAD, _lib.BF16, (ctypes.c_int * 3)(R, N, K), plan), 'mf_plan')
+    u = 2.0 ** -24
+    ref_y, mag_y = xb @ wb.t() + b.double(), xb.abs() @ wb.abs().t() + b.double().abs()
+    rs = dict(y=_worst_ratio(y, ref_y, (K / 8 + 10) * u * mag_y),
+              yr=_worst_ratio(yr, ref_y + res.double(), (K / 8 + 10) * u * (mag_y + res.double().abs())),
+              dx=_worst_ratio(dx, dyb @ wb, (N / 8 + 10) * u * (dyb.abs() @ wb.abs())),
+              dw=_worst_ratio(dw, dyb.t() @ xb, (R / 8 + plan[7] + 4) * u * (dyb.abs().t() @ xb.abs())))
+    return result(f'pointwise_exact[bf16 R{R} K{K} N{N}]', max(rs.values()), 1.0,
+                  'worst |got - ref| / bound: ' + ' '.join(f'{k} {v:.3f}' for k, v in rs.items()) + f'; {plan[7]} slabs')
+
+
+def check_wgrad_exact(stride, N, S, Ca, Cb, Ya, Yb, thr, sliced, seed=0):
+    """bf16 weight gradient with NORMALISED sources (stride 1: ops.wgrad under threshold thr; stride 2: ops.wgrad_s2) on N(0, 1) operands against the
+    float64 gradient on the operands the kernel multiplies: x_hat = _xhat_bf16(x, mr), the kernels' prologue restated (f32 fma, one rounding to bf16), not
+    a float64 normalisation rounded afterwards.  Per element |got - ref| <= (R / 8 + splits + 4) 2^-24 sum|x_hat||dy|, R the voxels the reduction runs
+    over (N x the dY grid): one f32 rounding per MFMA k-step and lane half, one per slab of the reduction, slack 4 (check_conv_exact's).  At R <= 4096
+    one missing voxel is several bounds.  err = the worst ratio, <= 1; an element over 1 may only be an exact f32 tie of the float64 fma (_xhat_bf16)."""
+    import exact_ref as er
+    from rsuper_amd.hip import ops
+    dt = torch.bfloat16
+    D, H, W = S
+    So = tuple(S) if stride == 1 else tuple((s + 1) // 2 for s in S)
+    xa = rnd(_rng_t(seed + 1, (N, Ca, D, H, W)) + 0.3, 'bf16')
+    xb = rnd(_rng_t(seed + 2, (N, Cb, D, H, W)) * 1.5 - 0.2, 'bf16') if Cb else None
+    o = dict(xa=xa, xb=xb, mra=stats_ref(xa), mrb=stats_ref(xb) if Cb else None, dy=rnd(_rng_t(seed + 6, (N, Ya + Yb) + So), 'bf16'))
+    xh = _xhat_bf16(xa, o['mra']) if xb is None else torch.cat([_xhat_bf16(xa, o['mra']), _xhat_bf16(xb, o['mrb'])], 1)
+    ref, mag = er.wgrad_f64(xh, o['dy'], stride), er.wgrad_f64(xh.abs(), o['dy'].abs(), stride)
+    sa, sb, y1, y2 = _wgrad_sources(o, dt, Ya, Yb, sliced)
+    dw1 = torch.full((Ya, Ca + Cb, 3, 3, 3), float('nan'), device=DEV)
+    dw2 = torch.full((Yb, Ca + Cb, 3, 3, 3), float('nan'), device=DEV) if Yb else None
+    if stride == 1:
+        with _wgrad_pins(thr, None) as L:
+            plan = _wgrad_launch_plan(L, dt, Ca, Cb, Ya, Yb, N, S, 0)
+            ops.wgrad(sa, sb, y1, y2, dw1, dw2, (N,) + tuple(S))
+            torch.cuda.synchronize()
+        splits = plan[1]
+    else:
+        splits = ops._L().rsuper_conv3_wgrad_s2_splits(ops._DT[dt], Ca, Ya + Yb, N, D, H, W)
+        plan = ('wgrad_s2', splits)
+        ops.wgrad_s2(sa, y1, y2, dw1, dw2, (N,) + tuple(S))
+        torch.cuda.synchronize()
+    R = N * So[0] * So[1] * So[2]
+    bound = (R / 8 + splits + 4) * 2.0 ** -24 * mag
+    got = dw1.cpu() if not Yb else torch.cat([dw1.cpu(), dw2.cpu()], 0)
+    ratio = _worst_ratio(got, ref, bound)
+    return result(f'wgrad_exact[bf16 stride{stride} thr{thr} N{N} S{S} {Ca}+{Cb}->{Ya}+{Yb}{" sliced" if sliced else ""}]', ratio, 1.0,
+                  f'worst |got - ref| / ((R / 8 + splits + 4) 2^-24 sum|x_hat||dy|) {ratio:.3f}; R {R}; plan {plan}')
+
+
 def all_checks(quick=False):
     cs = []
     for mode in ('f32', 'bf16'):
@@ -1543,4 +1744,12 @@ def all_checks(quick=False):
     cs += [(check_depthwise, (8, (6, 7, 9))), (check_depthwise, (72, (5, 4, 11), 1)), (check_depthwise, (256, (12, 12, 12))),
            (check_depthwise, (1280, (3, 3, 3)))]
     cs += [(check_medformer_tiny, ('f32',)), (check_medformer_tiny, ('bf16',))]
+    # integer operands, equal to float64 at every element (tests/exact_ref.py; the lists tests/test_gpu_exact_int.py runs): every kernel and configuration
+    # of the stride-1 weight-gradient plan, the strided weight gradient, csrc/pointwise.hip at every rung of its dispatch and on column slices; then the
+    # rounding of the same kernels on real operands at derived bounds
+    import exact_ref as er
+    from test_gpu_mf_kernels import POINTWISE
+    cs += [(check_wgrad_int, c) for c in er.WGRAD_INT] + [(check_wgrad_s2_int, c) for c in er.WGRAD_S2_INT]
+    cs += [(check_pointwise_int, c) for c in POINTWISE] + [(check_pointwise_int, c + (True,)) for c in er.POINTWISE_SLICED]
+    cs += [(check_pointwise_exact, c[1:]) for c in POINTWISE if c[0] == 'bf16' and c[1] <= 4160] + [(check_wgrad_exact, c) for c in er.WGRAD_EXACT]
     return cs
