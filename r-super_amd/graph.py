@@ -49,7 +49,7 @@ def _release_cached_blocks():
 
 
 def _capture_safe_blas():
-    """hipBLASLt (torch's default on ROCm) for the library GEMMs a capture records; MedFormer's per-call library choice off.
+    """hipBLASLt (torch's default on ROCm) for the library GEMMs a capture records.
     History: while the "garbage after a few replays" defect was being bisected, runs with rocBLAS preferred were corrupted in 6 of 15 cases and
     runs with hipBLASLt in 0 of 13, and this switch was taken for the fix.  It was not: the victim was a captured `hipMemsetAsync` node of this
     repo's own gradient-norm accumulator, which writes 0xC0 bytes after eager interludes (removed in csrc/optim.hip) -- with that
@@ -59,11 +59,6 @@ def _capture_safe_blas():
         return
     if torch.cuda.is_available() and hasattr(torch.backends.cuda, 'preferred_blas_library'):
         torch.backends.cuda.preferred_blas_library('cublaslt')
-    try:
-        from .model.dim3 import medformer_utils as _mu
-        _mu.gemm_library.active = False
-    except Exception:
-        pass
 
 
 def _refuse_branches(net, who):

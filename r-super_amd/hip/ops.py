@@ -1473,8 +1473,13 @@ def pointwise_wgrad(dy2, x2, want_bias, compute):
 
 def pointwise_supported(x, w):
     """Shapes the HIP pointwise GEMM takes (f32 rows on the GPU, channel counts multiples of 4, below 4 GiB)."""
-    return (x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0
-            and (x.numel() // x.shape[-1] + 1) * max(w.shape[0], w.shape[1]) * 4 < (1 << 32))
+    return (x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
+            and pointwise_shape_supported(x.numel() // x.shape[-1], w.shape[1], w.shape[0]))
+
+
+def pointwise_shape_supported(rows, cin, cout):
+    """The shape half of `pointwise_supported`, from the sizes alone: both channel counts multiples of 4, rows x the wider side below 4 GiB."""
+    return cout % 4 == 0 and cin % 4 == 0 and (rows + 1) * max(cout, cin) * 4 < (1 << 32)
 
 
 # ------------------------------------------------------------------------------------------------ multi-task / CLIP baselines

@@ -119,14 +119,6 @@ class MedFormer(nn.Module):
         self.classification_branch = branch(len(class_list_cls)) if classification_branch else None      # medformer.py:148-158, in this order
         self.clip_branch = branch(clip_feats) if clip_branch else None
         self.compute_dtype = compute_dtype or os.environ.get('RSUPER_DTYPE', 'bf16')
-        # RSUPER_MF_BLAS=cublas (opt-in): the fp32 library GEMMs that are left (81-token fusion transformer, aux head) through rocBLAS instead of
-        # torch's default hipBLASLt -- 7.5 vs 18.5 us of host time per call.  It was the default in round 2 and is NOT any more: it is a
-        # process-wide torch setting, and with the pointwise products on csrc/pointwise.hip it no longer pays.  (The replay corruption
-        # once attributed to captured rocBLAS launches was a captured memset node: DESIGN.md 3.4c.)
-        blas = os.environ.get('RSUPER_MF_BLAS', 'default')
-        if blas != 'default' and torch.cuda.is_available() and hasattr(torch.backends.cuda, 'preferred_blas_library'):
-            torch.backends.cuda.preferred_blas_library(blas)
-            _mu.gemm_library.active = blas == 'cublas'      # long reductions switch back to hipBLASLt per call (medformer_utils.gemm_library)
 
     def _dtype(self):
         return {'bf16': torch.bfloat16, 'f32': torch.float32}[self.compute_dtype]
@@ -136,12 +128,10 @@ class MedFormer(nn.Module):
             raise _lib.RSuperHipError('rsuper_amd MedFormer runs on MI355X only (no CPU fallback); move the input to cuda')
         _lib.require_device()
         dt = self._dtype()
-        # operand dtype of the 1x1x1 GEMMs in the attention stages: fp32 (RSUPER_MF_GEMM_BF16=1 rounds the operands to bf16 in the bf16 mode --
-        # measured SLOWER, 47-53 vs 44 ms/step: the casts around every GEMM cost more than the faster MFMA rate saves at these sizes)
-        _mu.GEMM_DTYPE = dt if os.environ.get('RSUPER_MF_GEMM_BF16') == '1' else torch.float32
+        # the 1x1x1 GEMMs of the attention stages keep fp32 storage (bf16 storage was measured, then removed: 47-53 vs 44 ms/step, the casts
+        # around every GEMM cost more than the faster MFMA rate saves at these sizes)
         _mu.GEMM_COMPUTE = dt                      # HIP pointwise GEMMs: bf16 MFMA operands in the bf16 mode, exact-f32 MFMA in the parity mode
-        if _mu.HIP_POINTWISE and os.environ.get('RSUPER_MF_PREPACK', '1') == '1':
-            ops.pointwise_prepack(dt)              # MFMA fragments of every 1x1x1 / linear weight of the attention stages: one launch per step
+        ops.pointwise_prepack(dt)                  # MFMA fragments of every 1x1x1 / linear weight of the attention stages: one launch per step
         x0 = self.inc(x, dt)
         x1, _ = self.down1(x0, dt)
         x2, m2 = self.down2(x1, dt)

@@ -89,68 +89,54 @@ def upsample_trilinear(x, size, planar=False):
 
 # RSUPER_MF_ATEN_ATTENTION=1: the ATen composition of the attention core instead of csrc/battn.hip (A/B switch; same results to fp32 rounding)
 FUSED_ATTENTION = os.environ.get('RSUPER_MF_ATEN_ATTENTION') != '1'
-HIP_POINTWISE = os.environ.get('RSUPER_MF_LIBRARY_GEMM') != '1'      # 1x1x1 convolutions / linear layers on csrc/pointwise.hip (=1: library GEMMs, A/B)
-FUSE_RESIDUAL = os.environ.get('RSUPER_MF_FUSE_RES', '1') == '1'          # identity shortcuts added in the pointwise GEMM's epilogue
-HIP_TOKEN_ATTN = os.environ.get('RSUPER_MF_TOKEN_ATTN', '1') == '1'       # fusion transformer's attention core on csrc/token_attn.hip (=0: the ATen chain, A/B)
-HIP_POINTWISE_WGRAD = os.environ.get('RSUPER_MF_LIBRARY_WGRAD') != '1'   # their weight / bias gradients too (=1: library GEMMs, A/B)
-HIP_MAP_PRODUCT = os.environ.get('RSUPER_MF_MAP_PRODUCT', '1') == '1'        # =0: the semantic-map product as a library GEMM (A/B)
-PAD_OUT_CHANNELS = os.environ.get('RSUPER_MF_PAD_HEAD', '1') == '1'           # =0: the aux head as a library GEMM (A/B)
-HIP_POINTWISE_MIN_ROWS = int(os.environ.get('RSUPER_MF_PW_MIN_ROWS', '32'))    # below (the 27-token maps): library GEMM
 GEMM_COMPUTE = torch.float32    # MFMA operand type of the HIP pointwise GEMMs: set per forward by MedFormer from its compute_dtype
-GEMM_DTYPE = torch.float32      # set per forward by MedFormer (opt-in bf16 operands for the 1x1x1 GEMMs, see medformer.py)
 
+POINTWISE_MIN_ROWS = 32         # fewer rows (the 27-token maps) are not worth an MFMA tile: ATen
 
 # weight gradients over at least MIN_ROWS voxels are split into slabs of at least MIN_SLAB voxels (measured: splitting the 12^3 stages too,
 # 3456 rows, or thinner slabs is slower -- 31.3 / 30.7 vs 30.1 ms per replayed step)
 SPLITK_MIN_ROWS, SPLITK_MIN_SLAB = 8192, 1024
 
 
-LT_MIN_K = 1024         # reductions at least this long go to hipBLASLt (see `gemm_library`; 512: 28.7, 2048: 28.7, 256: 29.7 vs 28.5 ms/step)
-
-
-class gemm_library:
-    """Per-call choice between the two GEMM libraries behind torch.mm / bmm.  MedFormer makes rocBLAS the process default (medformer.py:
-    7.5 vs 18.5 us of host time per call, faster kernels for the 54-row products and the wide-output expansions), but rocBLAS is slower on
-    long reductions with small outputs: 57 vs 25 us for the 1024 x 3456 x 256 weight gradients of the 12^3 stages, 47 vs 36 us for the
-    voxel-split weight gradients, 772 vs ~50 us for the semantic-map product (27 x 13824 x 128).  `with gemm_library(k):` switches to
-    hipBLASLt for the calls inside when the reduction length k reaches LT_MIN_K -- and only if MedFormer's default is active."""
-
-    active = False                                       # set by MedFormer when it selected rocBLAS as the default
-
-    def __init__(self, k):
-        self.on = gemm_library.active and k >= LT_MIN_K
-
-    def __enter__(self):
-        if self.on:
-            torch.backends.cuda.preferred_blas_library('cublaslt')
-
-    def __exit__(self, *exc):
-        if self.on:
-            torch.backends.cuda.preferred_blas_library('cublas')
-        return False
+def linear_route(is_cuda, dtype, rows, cin, cout, has_res):
+    """Which implementation `linear` gives rows x cin -> cout, from the sizes alone (`dtype`: of the rows; the weight has it too):
+    'hip'         csrc/pointwise.hip, forward and both gradients: f32 rows on the GPU, at least POINTWISE_MIN_ROWS of them, shapes of
+                  ops.pointwise_shape_supported;
+    'hip_padded'  the same on a weight padded with zero rows to the next multiple of 4 outputs (the 26-class deep-supervision head); the
+                  padded GEMM has no shortcut input, so only without `res`;
+    'library'     what is left of f32 from SPLITK_MIN_ROWS rows upwards (an input-channel count that is no multiple of 4): `_LinearFn` on
+                  library GEMMs, weight gradient split over slabs of the rows, bias gradient as a ones-row GEMM;
+    'aten'        the rest: F.linear (+ res)."""
+    f32 = dtype == torch.float32
+    if is_cuda and f32 and rows >= POINTWISE_MIN_ROWS:
+        if ops.pointwise_shape_supported(rows, cin, cout):
+            return 'hip'
+        if not has_res and cout % 4 and ops.pointwise_shape_supported(rows, cin, cout + (-cout) % 4):
+            return 'hip_padded'
+    return 'library' if f32 and rows >= SPLITK_MIN_ROWS else 'aten'
 
 
 class _LinearFn(torch.autograd.Function):
-    """F.linear with the three GEMMs issued explicitly: each through the faster library for its shape (`gemm_library`), and the weight
-    gradient dW = dy^T x of the high-resolution stages as a batched GEMM over slabs of the voxel axis followed by a sum.  The library runs
+    """F.linear with its three GEMMs issued explicitly.  hip: csrc/pointwise.hip.  Otherwise library GEMMs, with the weight gradient
+    dW = dy^T x of the high-resolution stages as a batched GEMM over slabs of the voxel axis followed by a sum.  The library runs
     dy^T x as ONE GEMM with (Cout / 32) x (Cin / 128) workgroups however long the reduction is: at 24^3 x 2 voxels that is 16 workgroups
-    on 256 CUs, 186 us for a 128 x 27648 x 512 product (3.4 ms per MedFormer step over all such layers); split 16-way it takes ~35 us."""
+    on 256 CUs, 186 us for a 128 x 27648 x 512 product; split 16-way it takes ~35 us."""
 
     @staticmethod
-    def forward(ctx, x, w, b, res=None, compute=None):
-        """res: a tensor of the output's shape added to it (identity shortcut) -- in the GEMM's epilogue on the HIP path; its gradient is dy.
-        compute: MFMA operand type of the HIP GEMMs of this call (None: the module-wide GEMM_COMPUTE of the running MedFormer)."""
+    def forward(ctx, x, w, b, res, compute, hip):
+        """res: a tensor of the output's shape added to it (identity shortcut) or None -- in the GEMM's epilogue on the HIP path; its gradient
+        is dy.  compute: MFMA operand type of the HIP GEMMs of this call (None: the module-wide GEMM_COMPUTE of the running MedFormer).
+        hip: `linear`'s decision (linear_route)."""
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         ctx.has_res = res is not None
-        ctx.hip = HIP_POINTWISE and x.numel() // x.shape[-1] >= HIP_POINTWISE_MIN_ROWS and ops.pointwise_supported(x, w)
+        ctx.hip = hip
         ctx.compute = GEMM_COMPUTE if compute is None else compute
-        if ctx.hip:          # csrc/pointwise.hip: MFMA GEMM straight from the row-major rows (no library call, no staging copies)
+        if hip:              # MFMA GEMM straight from the row-major rows (no library call, no staging copies)
             wc = w.contiguous()
             r2 = None if res is None else res.reshape(-1, w.shape[0]).contiguous()
             return ops.pointwise_gemm(x.reshape(-1, x.shape[-1]).contiguous(), wc, b, 0, ctx.compute, r2).reshape(*x.shape[:-1], w.shape[0])
-        with gemm_library(w.shape[1]):
-            y = F.linear(x, w, b)
+        y = F.linear(x, w, b)
         return y if res is None else y + res
 
     @staticmethod
@@ -158,41 +144,34 @@ class _LinearFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy2, x2 = dy.reshape(-1, dy.shape[-1]), x.reshape(-1, x.shape[-1])
         dx = dw = db = None
+        dres = dy if ctx.has_res else None
         if ctx.needs_input_grad[0]:
-            if ctx.hip:
-                dx = ops.pointwise_gemm(dy2.contiguous(), w.contiguous(), None, 1, ctx.compute).reshape(x.shape)
-            else:
-                with gemm_library(w.shape[0]):
-                    dx = torch.mm(dy2, w).reshape(x.shape)
+            dx = (ops.pointwise_gemm(dy2.contiguous(), w.contiguous(), None, 1, ctx.compute) if ctx.hip else torch.mm(dy2, w)).reshape(x.shape)
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.hip and HIP_POINTWISE_WGRAD and ctx.needs_input_grad[1]:
+        if ctx.hip and ctx.needs_input_grad[1]:
             # csrc/pointwise.hip: dW and db from one pass over dy and x (slabs of the rows, added in slab order)
             dw, db = ops.pointwise_wgrad(dy2.contiguous(), x2.contiguous(), want_db, ctx.compute)
-            return dx, dw, db, (dy if ctx.has_res else None), None
+            return dx, dw, db, dres, None, None
         if ctx.needs_input_grad[1]:
             rows = x2.shape[0]
             slabs = next((s for s in (32, 16, 8, 4) if rows % s == 0 and rows // s >= SPLITK_MIN_SLAB), 0) if rows >= SPLITK_MIN_ROWS else 0
             if slabs:
-                with gemm_library(rows // slabs):
-                    dw = torch.bmm(dy2.reshape(slabs, rows // slabs, -1).transpose(1, 2), x2.reshape(slabs, rows // slabs, -1)).sum(0)
+                dw = torch.bmm(dy2.reshape(slabs, rows // slabs, -1).transpose(1, 2), x2.reshape(slabs, rows // slabs, -1)).sum(0)
             else:
-                with gemm_library(rows):
-                    dw = torch.mm(dy2.t(), x2)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            if dy2.shape[0] >= 4096 and not _ATEN_BIAS_SUM:
+                dw = torch.mm(dy2.t(), x2)
+        if want_db:
+            if dy2.shape[0] >= 4096:
                 # Column sums of a tall matrix as a 1 x rows GEMM, NOT `dy2.sum(0)`: ATen's multi-block reduction (global partials + semaphores)
-                # returned garbage from the 12th replay on when captured in a hipGraph on this ROCm (the aux head's bias gradient, 27648 x 26:
+                # returned garbage from the 12th replay on when captured in a hipGraph on this ROCm (a bias gradient over 27648 x 26:
                 # ~-2e-10 instead of ~2e-3, every later replay too; eager and the first 11 replays correct) -- found by comparing eager and
-                # replayed training runs gradient by gradient (tests/test_gpu_edge.py::test_graphed_network_many_replays_match_eager).
-                with gemm_library(dy2.shape[0]):
-                    db = torch.mm(_ones_row(dy2.shape[0], dy2.device), dy2).reshape(-1)
+                # replayed training runs gradient by gradient (tests/test_gpu_edge.py::test_graphed_linear_library_arm_replays_match_eager).
+                db = torch.mm(_ones_row(dy2.shape[0], dy2.device), dy2).reshape(-1)
             else:
                 db = dy2.sum(0)
-        return dx, dw, db, (dy if ctx.has_res else None), None
+        return dx, dw, db, dres, None, None
 
 
 _ONES = {}
-_ATEN_BIAS_SUM = os.environ.get('RSUPER_DEBUG_ATEN_BIAS_SUM') == '1'      # reproduce the captured-reduction defect (see _LinearFn.backward)
 
 
 def _ones_row(n, device):
@@ -203,37 +182,24 @@ def _ones_row(n, device):
 
 
 def linear(x, w, b=None, res=None, compute=None):
-    """F.linear(x, w, b) [+ res]: the shortcut addition rides in the HIP GEMM's epilogue (RSUPER_MF_FUSE_RES=0: a separate add, A/B).
+    """F.linear(x, w, b) [+ res] by the one decision of `linear_route`; on the HIP GEMM the shortcut addition rides in the epilogue.
     compute: operand type of the HIP GEMM for this call (None: GEMM_COMPUTE)."""
-    rows = x.numel() // x.shape[-1]
-    if res is not None and not FUSE_RESIDUAL:
-        return linear(x, w, b, None, compute) + res
-    if HIP_POINTWISE and rows >= HIP_POINTWISE_MIN_ROWS and ops.pointwise_supported(x, w):
-        return _LinearFn.apply(x, w, b, res, compute)
-    if HIP_POINTWISE and PAD_OUT_CHANNELS and res is None and rows >= HIP_POINTWISE_MIN_ROWS and w.shape[0] % 4 and w.shape[1] % 4 == 0 and x.is_cuda \
-            and x.dtype == torch.float32:
-        # an output-channel count that is not a multiple of 4 (the 26-class deep-supervision head, medformer.py:190-194): zero rows pad the weight to the next
-        # multiple, the GEMM runs on csrc/pointwise.hip like every other 1x1x1 convolution and the padding columns are dropped (their gradient is zero)
+    route = linear_route(x.is_cuda, x.dtype, x.numel() // x.shape[-1], w.shape[1], w.shape[0], res is not None)
+    if route == 'hip_padded':
+        # zero rows pad the weight to the next multiple of 4, the padding columns are dropped (their gradient is zero)
         n, padn = w.shape[0], (-w.shape[0]) % 4
         wp = torch.cat([w, w.new_zeros((padn, w.shape[1]))], 0)
         bp = None if b is None else torch.cat([b, b.new_zeros(padn)])
-        if ops.pointwise_supported(x, wp):
-            return _LinearFn.apply(x, wp, bp, None, compute)[..., :n]
-    if x.dtype == torch.float32 and (rows >= SPLITK_MIN_ROWS or (gemm_library.active and max(rows, w.shape[0], w.shape[1]) >= LT_MIN_K)):
-        return _LinearFn.apply(x, w, b, res, compute)
+        return _LinearFn.apply(x, wp, bp, None, compute, True)[..., :n]
+    if route != 'aten':
+        return _LinearFn.apply(x, w, b, res, compute, route == 'hip')
     y = F.linear(x, w, b)
     return y if res is None else y + res
 
 
 def pointwise(x, conv, res=None, compute=None):
-    """Conv3d(k=1) as a GEMM over the channel axis (csrc/pointwise.hip, forward and both gradients; library GEMMs below 32 rows / for channel
-    counts that are not multiples of 4); fp32 storage unless GEMM_DTYPE says bf16 (opt-in experiment).  res: shortcut added to the output."""
-    w = conv.weight.reshape(conv.weight.shape[0], conv.weight.shape[1])
-    if GEMM_DTYPE != torch.float32 and x.numel() // x.shape[-1] >= 64:
-        y = F.linear(x.to(GEMM_DTYPE), w.to(GEMM_DTYPE)).float()
-        y = y if conv.bias is None else y + conv.bias
-        return y if res is None else y + res
-    return linear(x, w, conv.bias, res, compute)
+    """Conv3d(k=1) as `linear` over the channel axis, fp32 storage.  res: shortcut added to the output."""
+    return linear(x, conv.weight.reshape(conv.weight.shape[0], conv.weight.shape[1]), conv.bias, res, compute)
 
 
 def depthwise(x, conv):
@@ -445,15 +411,14 @@ class SemanticMapGeneration(nn.Module):
             w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
         y = ops.Conv3Fn.apply(x, w).float().flatten(1, 3)                       # (B, voxels, md + codes + pad)
         kc = codes + pad
-        if HIP_POINTWISE and HIP_MAP_PRODUCT and md % 4 == 0 and kc % 4 == 0 and y.is_cuda and y.shape[1] >= HIP_POINTWISE_MIN_ROWS:
+        if md % 4 == 0 and kc % 4 == 0 and y.is_cuda and y.shape[1] >= POINTWISE_MIN_ROWS:
             # soft-max over the voxels of every code column (the `pad` columns come from zero weight rows: uniform weights, their map rows are dropped)
             # (soft-max over the LAST axis of the transposed view: ATen's soft-max over a middle axis with 32 inner elements runs 64 threads in all --
             # 27.2 instead of 25.4 ms per replayed step when the product moved here first)
             wv = F.softmax(y[..., md:md + kc].transpose(1, 2), dim=-1).transpose(1, 2).contiguous()      # (B, voxels, kc)
             return _MapProductFn.apply(wv, y[..., :md])[:, :codes].reshape(x.shape[0], *self.map_size, md)
         weight = F.softmax(y[..., md:md + codes].transpose(1, 2), dim=-1)       # (B, codes, voxels): softmax over the voxels of a code
-        with gemm_library(weight.shape[-1]):                                    # 27 x voxels x map_dim: a long reduction into a tiny output
-            return torch.matmul(weight, y[..., :md]).reshape(x.shape[0], *self.map_size, md)
+        return torch.matmul(weight, y[..., :md]).reshape(x.shape[0], *self.map_size, md)      # 27 x voxels x map_dim
 
 
 class _PreNorm(nn.Module):
@@ -477,7 +442,7 @@ class _TokenAttention(nn.Module):
         B, L, _ = x.shape
         # projections through linear(): csrc/pointwise.hip (162 token rows: reduction split over the waves), shortcut in the epilogue
         qkv = linear(x, self.to_qkv.weight, compute=compute)
-        if HIP_TOKEN_ATTN and qkv.is_cuda and ops.token_attn_supported(L, qkv.shape[-1] // (3 * self.heads)):
+        if qkv.is_cuda and ops.token_attn_supported(L, qkv.shape[-1] // (3 * self.heads)):
             # score / soft-max / mixing in one launch per direction, no transposing copies (csrc/token_attn.hip)
             o = ops.TokenAttnFn.apply(qkv, self.heads, self.scale)
         else:

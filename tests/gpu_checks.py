@@ -817,8 +817,8 @@ def check_squeeze_excite(C, dims, N=2, seed=93):
 
 
 def check_linear_splitk(rows, cin, cout, bias, seed=99):
-    """1x1x1 convolution of the attention stages with the voxel-split weight gradient (model/dim3/medformer_utils.py linear) against
-    F.linear in float64 on the CPU: output and the three gradients."""
+    """1x1x1 convolution of the attention stages at row counts of the high-resolution stages (model/dim3/medformer_utils.py linear: the
+    'hip' arm, slab-split weight gradient of csrc/pointwise.hip) against F.linear in float64 on the CPU: output and the three gradients."""
     from rsuper_amd.model.dim3 import medformer_utils as mu
     x = _rng_t(seed, (2, rows // 2, cin)).requires_grad_(True)
     w = _rng_t(seed + 1, (cout, cin), 0.2).requires_grad_(True)
@@ -828,17 +828,10 @@ def check_linear_splitk(rows, cin, cout, bias, seed=99):
     (y_ref * go.double()).sum().backward()
     xd, wd = x.detach().to(DEV).requires_grad_(True), w.detach().to(DEV).requires_grad_(True)
     bd = b.detach().to(DEV).requires_grad_(True) if bias else None
-    assert rows >= mu.SPLITK_MIN_ROWS
-    prev, was = torch.backends.cuda.preferred_blas_library(), mu.gemm_library.active
-    mu.gemm_library.active = True                       # the per-call library switch of the opt-in rocBLAS mode (RSUPER_MF_BLAS=cublas)
-    torch.backends.cuda.preferred_blas_library('cublas')
-    try:
-        y = mu.linear(xd, wd, bd)
-        (y * go.to(DEV)).sum().backward()
-        torch.cuda.synchronize()
-    finally:                                            # process-wide setting: leave it as it was for the checks that follow
-        mu.gemm_library.active = was
-        torch.backends.cuda.preferred_blas_library(prev)
+    assert rows >= mu.SPLITK_MIN_ROWS and mu.linear_route(True, torch.float32, rows, cin, cout, False) == 'hip'
+    y = mu.linear(xd, wd, bd)
+    (y * go.to(DEV)).sum().backward()
+    torch.cuda.synchronize()
     errs = [relerr(y.detach().cpu(), y_ref.detach().float()), relerr(xd.grad.cpu(), x.grad), relerr(wd.grad.cpu(), w.grad)]
     if bias:
         errs.append(relerr(bd.grad.cpu(), b.grad))

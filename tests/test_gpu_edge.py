@@ -676,36 +676,6 @@ def test_augmented_loader_feeds_packed_ingest(tmp_path):
 
 
 @pytest.mark.gpu
-def test_gemm_library_switch_is_scoped():
-    """medformer_utils.gemm_library: hipBLASLt for the calls inside the block when the reduction is long and MedFormer's rocBLAS default is
-    active, the default restored afterwards (also on an exception); inactive -> never touches the process setting."""
-    from rsuper_amd.model.dim3 import medformer_utils as mu
-    get = torch.backends.cuda.preferred_blas_library
-    before, was_active = get(), mu.gemm_library.active
-    try:
-        mu.gemm_library.active = True
-        get('cublas')
-        with mu.gemm_library(mu.LT_MIN_K):
-            assert 'lt' in str(get()).lower()
-            y = torch.mm(torch.ones(8, mu.LT_MIN_K, device='cuda'), torch.ones(mu.LT_MIN_K, 8, device='cuda'))
-        assert 'lt' not in str(get()).lower() and float(y[0, 0]) == mu.LT_MIN_K
-        with mu.gemm_library(mu.LT_MIN_K - 1):
-            assert 'lt' not in str(get()).lower()
-        with pytest.raises(ZeroDivisionError):
-            with mu.gemm_library(4 * mu.LT_MIN_K):
-                1 / 0
-        assert 'lt' not in str(get()).lower()
-        mu.gemm_library.active = False
-        get('cublaslt')
-        with mu.gemm_library(4 * mu.LT_MIN_K):
-            pass
-        assert 'lt' in str(get()).lower()
-    finally:
-        mu.gemm_library.active = was_active
-        get(before)
-
-
-@pytest.mark.gpu
 def test_medformer_shipped_widths_match_oracle_f32():
     """The SHIPPED MedFormer widths (config/abdomenatlas_ufo/medformer_3d.yaml: base 32, channels 64..320, 4 / 8 / 10 heads of 32, 27 map
     tokens, fusion depth 2) -- the shapes the fused attention core is built for, which the tiny fixture (8 tokens, heads of 16) does not
@@ -956,10 +926,8 @@ def test_graphed_step_matches_eager(model):
     st_e, st_g = next(iter(opt_e.state.values())), next(iter(opt_g.state.values()))
     assert int(st_e['step']) == int(st_g['step']) == 16
     if model == 'medformer':
-        # captures never record rocBLAS launches (rsuper_amd.graph._capture_safe_blas: the root cause of round 2's "garbage after a few
-        # replays"): the process is on hipBLASLt and MedFormer's per-call library switch is off after a capture
-        from rsuper_amd.model.dim3 import medformer_utils as mu
-        assert 'lt' in str(torch.backends.cuda.preferred_blas_library()).lower() and mu.gemm_library.active is False
+        # captures never record rocBLAS launches (rsuper_amd.graph._capture_safe_blas): the process is on hipBLASLt after a capture
+        assert 'lt' in str(torch.backends.cuda.preferred_blas_library()).lower()
     with pytest.raises(ValueError):
         GraphedTrainStep(*build(), argparse.Namespace(**{**vars(largs), 'report_volume_loss_basic': 0.1}), classes)
     with pytest.raises(ValueError):                                   # the optimiser state must exist before the capture
@@ -1060,11 +1028,13 @@ def test_graphed_step_without_per_step_sync_matches_eager():
 
 @pytest.mark.gpu
 def test_graphed_network_many_replays_match_eager():
-    """More than a dozen replays of the forward / backward graphs of a MedFormer whose deep-supervision head is tall enough (8192 rows)
-    for the GEMM form of its bias gradient: losses and gradient norms equal to the eager run at EVERY step.  Regression test for a defect
-    of captured ATen multi-block reductions on this ROCm -- `dy.sum(0)` over 27648 rows returned garbage from the 12th replay of a hipGraph
-    on (eager and the first 11 replays were right), found by comparing an eager and a replayed full-size run gradient by gradient; the tall
-    bias gradients are now a 1 x rows GEMM (model/dim3/medformer_utils.py _LinearFn)."""
+    """More than a dozen replays of the forward / backward graphs of a MedFormer with a tall deep-supervision head (8192 rows): losses and
+    gradient norms equal to the eager run at EVERY step.  Written as the regression test for a defect of captured ATen multi-block
+    reductions on this ROCm -- `dy.sum(0)` over 27648 rows returned garbage from the 12th replay of a hipGraph on (eager and the first 11
+    replays were right), found by comparing an eager and a replayed full-size run gradient by gradient.  Since the head's 5 (or 26) outputs
+    are padded to a multiple of 4 it runs on csrc/pointwise.hip and its bias gradient comes from `rsuper_pointwise_wgrad`, so this network
+    holds no tall ATen reduction any more; the 1 x rows GEMM that replaced `dy.sum(0)` on the library arm of `linear` is replayed by
+    test_graphed_linear_library_arm_replays_match_eager below."""
     import argparse
     import synth
     from rsuper_amd.graph import GraphedNetwork
@@ -1081,7 +1051,9 @@ def test_graphed_network_many_replays_match_eager():
     batch = dict(image=torch.from_numpy(synth.image(2, S, seed=9)).to('cuda'), label=torch.from_numpy(bt['label']).to('cuda'),
                  unk_channels=torch.from_numpy(bt['unk_channels']).to('cuda'), mask=torch.from_numpy(bt['mask']).to('cuda'),
                  volumes=torch.from_numpy(bt['volumes']).to('cuda'), diameters=torch.from_numpy(bt['diameters']).to('cuda'))
-    assert 2 * (S // 4) ** 3 >= 4096 >= 1 and mu.SPLITK_MIN_ROWS <= 2 * (S // 4) ** 3      # the aux head takes _LinearFn with the GEMM bias gradient
+    # the aux head is as tall as the library arm's split weight gradient and GEMM bias gradient ask, and takes the padded HIP GEMM
+    assert 2 * (S // 4) ** 3 >= 4096 >= 1 and mu.SPLITK_MIN_ROWS <= 2 * (S // 4) ** 3
+    assert mu.linear_route(True, torch.float32, 2 * (S // 4) ** 3, synth.MEDFORMER_TINY['chan_num'][5], len(classes), False) == 'hip_padded'
 
     def run(graphed):
         torch.manual_seed(0)
@@ -1097,6 +1069,81 @@ def test_graphed_network_many_replays_match_eager():
 
     h_e, h_g = run(False), run(True)
     assert h_e == h_g, [(i, a, b) for i, (a, b) in enumerate(zip(h_e, h_g)) if a != b][:3]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('route,rows,cin,cout,bias,res,compute', [
+    ('hip', 32, 8, 8, True, True, 'f32'), ('hip', 32, 8, 8, True, True, 'bf16'),
+    ('hip_padded', 32, 8, 6, True, False, 'f32'), ('hip_padded', 32, 8, 6, True, False, 'bf16'),
+    ('aten', 31, 8, 8, True, True, 'f32'),
+    ('library', 8192, 6, 6, True, False, 'f32'), ('library', 8192, 8, 6, False, True, 'f32')])
+def test_linear_every_route_matches_float64(monkeypatch, route, rows, cin, cout, bias, res, compute):
+    """medformer_utils.linear on each arm of linear_route at the smallest shape that selects it: output, dx, dw, db and dres against
+    F.linear in float64, 2e-5 of the reference's scale for f32 arithmetic (gpu_checks.check_linear_splitk), 1.5e-2 for bf16 MFMA operands
+    (gpu_checks.check_pointwise).  The library arm's bias gradient over >= 4096 rows is the ones-row GEMM, not `dy.sum(0)`."""
+    from rsuper_amd.model.dim3 import medformer_utils as mu
+    assert mu.linear_route(True, torch.float32, rows, cin, cout, res) == route
+    g = torch.Generator().manual_seed(rows + 7 * cout)
+    ts = dict(x=torch.randn(rows, cin, generator=g), w=torch.randn(cout, cin, generator=g) / math.sqrt(cin), go=torch.randn(rows, cout, generator=g))
+    if bias:
+        ts['b'] = torch.randn(cout, generator=g)
+    if res:
+        ts['r'] = torch.randn(rows, cout, generator=g)
+    leaves = [k for k in ts if k != 'go']
+
+    def run(dev, dt, fn):
+        t = {k: v.to(dev, dt).requires_grad_(k != 'go') for k, v in ts.items()}
+        y = fn(t['x'], t['w'], t.get('b'), t.get('r'))
+        return [y.detach()] + list(torch.autograd.grad(y, [t[k] for k in leaves], t['go']))
+
+    ones_rows = []
+    real = mu._ones_row
+    monkeypatch.setattr(mu, '_ones_row', lambda n, device: ones_rows.append(n) or real(n, device))
+    want = run('cpu', torch.float64, lambda x, w, b, r: F.linear(x, w, b) + (0 if r is None else r))
+    got = run(DEV, torch.float32, lambda x, w, b, r: mu.linear(x, w, b, r, compute=gc.DT[compute]))
+    torch.cuda.synchronize()
+    assert ones_rows == ([rows] if route == 'library' and bias else [])
+    tol = 2e-5 if compute == 'f32' else 1.5e-2
+    for name, a, e in zip(['y'] + ['d' + k for k in leaves], got, want):
+        assert a.shape == e.shape and gc.relerr(a.cpu(), e) <= tol, (name, gc.relerr(a.cpu(), e), tol)
+
+
+@pytest.mark.gpu
+def test_graphed_linear_library_arm_replays_match_eager():
+    """The library arm of medformer_utils.linear (6 input channels: no multiple of 4) at 8192 rows with a bias, forward and backward
+    captured in ONE single-branch hipGraph and replayed 16 times with fresh inputs: output and the three gradients equal to the eager
+    call at every replay.  Its bias gradient is the 1 x rows GEMM that replaced `dy.sum(0)`, whose captured ATen reduction went wrong from
+    the 12th replay on (test_graphed_network_many_replays_match_eager)."""
+    from rsuper_amd.model.dim3 import medformer_utils as mu
+    rows, cin, cout = 8192, 6, 6
+    assert mu.linear_route(True, torch.float32, rows, cin, cout, False) == 'library' and rows >= 4096
+    g = torch.Generator().manual_seed(17)
+    w = (torch.randn(cout, cin, generator=g) * 0.3).to(DEV).requires_grad_(True)
+    b = torch.randn(cout, generator=g).to(DEV).requires_grad_(True)
+    xs, gos = torch.randn(17, rows, cin, generator=g).to(DEV), torch.randn(17, rows, cout, generator=g).to(DEV)
+    x, go = xs[16].clone().requires_grad_(True), gos[16].clone()
+
+    def step():
+        y = mu.linear(x, w, b)
+        return (y,) + torch.autograd.grad(y, (x, w, b), go)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):                                    # warm-up off the capture: library handles, workspaces, the ones row
+        step()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        static = step()
+    for i in range(16):
+        with torch.no_grad():
+            x.copy_(xs[i]); go.copy_(gos[i])
+        graph.replay()
+        got = [t.clone() for t in static]
+        want = step()
+        torch.cuda.synchronize()
+        for name, a, e in zip(('y', 'dx', 'dw', 'db'), got, want):
+            assert torch.equal(a, e), (i, name, float((a - e).abs().max()))
 
 
 @pytest.mark.gpu

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Stand-alone probe of the defect behind DESIGN.md 3.4 (ii): an ATen multi-block reduction captured in a hipGraph.  Captures `y = x.sum(0)` for a
 (27648, 26) tensor, replays it with different kinds of eager work between the replays and reports the first replay whose result is wrong.
-Result on this ROCm 7.0 / PyTorch 2.10 build: all variants stay correct -- the defect needs the context of the training step (it shows with
-RSUPER_DEBUG_ATEN_BIAS_SUM=1 in `tools/medformer_step.py 60 bf16 netgraph-report`, where GraphedNetwork's self-verification reports it at
-replay 12, and never without eager GPU work between the replays).  Kept as the starting point for a minimal reproducer.
+Result on this ROCm 7.0 / PyTorch 2.10 build: all variants stay correct -- the defect needs the context of the training step (it showed in
+`tools/medformer_step.py 60 bf16 netgraph-report` while the aux head's bias gradient was `dy.sum(0)`, where GraphedNetwork's self-verification
+reported it at replay 12, and never without eager GPU work between the replays; that head now runs on csrc/pointwise.hip).  Kept as the starting point for a minimal reproducer.
 Usage: python tools/repro_graph_reduce.py"""
 import torch
 
